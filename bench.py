@@ -20,17 +20,29 @@ trajectories dealt out over the ranks (`frames // N` per GPU), which is what BAS
 `--scaling weak` gives every rank its own 10M x 512 shard instead.  `value` = total frames / max-over-ranks step time.
 Data is generated on the device before timing (AR(1) slow modes mixed into 512 features).
 
+A plain run sets up, warms up, times the --steps steps and prints the line; everything else runs only with --full.
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed (rank 0's share) as float64
+                         DIR/<name>.npy: the tICA model's eigenvalues / components / means, KCenters' centres, ids and
+                         inertia, and a fixed, seeded sample of rows of the projection, of labels_ / distances_ and of
+                         the predicted labels (every row index listed in transform_sample_rows.npy).  The inputs are seeded:
+                         two builds run with the same arguments can be compared array for array.
+    --full               also the secondary measurements and checks listed below (--no-cpu-baseline, --no-mbk and
+                         --no-extras leave parts of them out)
+
 Prints ONE JSON line on rank 0.  Besides the contract's keys:
   roofline      dominant kernel (the MFMA accumulation): `achieved` = the MFMA flop it EXECUTES / its HIP-event duration,
                 `frac` = achieved / dense fp32-MFMA peak (pipe utilisation); `algorithmic` = SURVEY 8(d)'s 4 F^2 flop per
                 frame / the same duration (can exceed the peak: the sum/difference kernel needs 0.625 of those flops)
   phases_ms     per-phase wall times (host clock around synchronised phases), summing to the step
+With --full only:
   self_check    the HIP path and the float64 oracle fitted on the same 64 trajectories (eigenvalues, rtol 1e-5), and the
                 full run's leading eigenvalues against that sample (loose)
   cpu_baseline  the oracle on the host cores (bounded sample): all-threads and 1-thread BLAS tICA, single-thread and
                 row-parallel exact KCenters, scikit-learn's own MiniBatchKMeans(k=1000)
   f64, config2, config1_width[_f64], config3_width, config3_stress, kcenters_wide_1m, config4_label_wide, config5_width,
-  config5_per_gpu, minibatchkmeans, strong_scaling_model   untimed secondary legs (N = 1 only)
+  config5_per_gpu, minibatchkmeans, h2d_inclusive, strong_scaling_model   untimed secondary legs (N = 1 only)
+  comm_measured_us, weak_scaling   collective latencies and the weak-scaling leg (N > 1 only)
 """
 import argparse
 import ctypes as C
@@ -257,6 +269,37 @@ def cpu_baseline(X_host_list, lag, k_comp, k_clusters, budget_s=8.0):
     return out, o, used
 
 
+def dump_outputs(path, tica, Y, kc, labels, max_bytes=48 << 20):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as float64 .npy files.  The model
+    arrays are written whole; the per-frame outputs (the [frames, k] projection, labels_, distances_, the predicted
+    labels) are sampled at the same rows, drawn with a fixed seed and sorted, as many as fit in what `max_bytes` leaves
+    after the model arrays (at least one)."""
+    def host(a):
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        return np.ascontiguousarray(a, dtype=np.float64)
+
+    def rows_of(a):
+        return host(a.index_select(0, idx_dev) if hasattr(a, "index_select") else np.asarray(a)[rows])
+
+    arrays = {"tica_eigenvalues": host(tica.eigenvalues_), "tica_components": host(tica.components_),
+              "tica_means": host(tica.means_), "kcenters_cluster_centers": host(kc.cluster_centers_),
+              "kcenters_cluster_ids": host(kc.cluster_ids_), "kcenters_inertia": host([kc.inertia_])}
+    n, k = Y.shape
+    left = max_bytes - sum(a.nbytes for a in arrays.values())
+    n_rows = min(n, max(1, left // (8 * (k + 4))))      # per row: k projection values, its index, 3 labels / distances
+    rows = np.sort(np.random.default_rng(0).choice(n, n_rows, replace=False))
+    idx_dev = None
+    if hasattr(Y, "index_select"):
+        import torch
+        idx_dev = torch.from_numpy(rows).to(Y.device)
+    arrays.update({"transform_sample_rows": host(rows), "transform_sample": rows_of(Y),
+                   "kcenters_labels_sample": rows_of(kc.labels_[0]), "kcenters_distances_sample": rows_of(kc.distances_[0]),
+                   "predict_labels_sample": rows_of(labels)})
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script under torch.distributed.run on a free
     local port and hand its exit code back.  When the node shows fewer devices than ranks (a 1-GPU test box) the ranks
@@ -311,7 +354,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mbk", action="store_true", help="skip the untimed MiniBatchKMeans(k=1000) leg")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed f64 / config2 / config5 / model legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (CPU baseline, self-check, other legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     os.environ["MSMBUILDER_AMD_TICA_MODE"] = args.mode
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -395,6 +443,8 @@ def main():
 
     times = {}
     elapsed, (ev, labels, kc, Y, tica) = timed(times, seqs, X, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tica, Y, kc, labels)
     # which transport the library's own collectives ran on: msm_comm_info -> (rank, world, kind 0 none / 1 RCCL / 2 host)
     ci = [C.c_int(0), C.c_int(1), C.c_int(0)]
     _lib.lib().msm_comm_info(C.byref(ci[0]), C.byref(ci[1]), C.byref(ci[2]))
@@ -417,7 +467,7 @@ def main():
     # MEASURED on this run's communicator -- RCCL over xGMI on a node with a GPU per rank -- for the sizes the step uses: the
     # tICA all-reduce (2 F^2 + 2 F doubles), the k-centers candidate all-gather and the k-centers round record
     comm_measured = None
-    if world > 1 and ci[2].value != 0:
+    if args.full and world > 1 and ci[2].value != 0:
         comm_measured = {"transport": comm_kind}
         rec_bytes = 8 * (48 + 1024 * (2 + args.components))
         for name, kind, nbytes in (("allreduce_tica_%dKB" % ((2 * F * F + 2 * F) * 8 // 1024), 0, (2 * F * F + 2 * F) * 8),
@@ -428,7 +478,7 @@ def main():
             comm_measured[name + "_us"] = float(us.value) if rc_m == 0 else None
 
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_extras:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_extras:
         # the other reading of "N GPUs", untimed secondary leg: every rank its own full-size shard (weak scaling)
         del labels, kc, Y, tica, seqs, X
         torch.cuda.empty_cache()
@@ -526,8 +576,8 @@ def main():
                              "kcenters_streamed_bytes_per_fit": kc_bytes,
                              "kcenters_pass_TBps_per_gpu": kc_bytes / fit_s / 1e12, "hbm_peak_TBps": 8.0}
 
-        extras = world == 1 and not args.no_extras
-        if world == 1 and not args.no_mbk:
+        extras = args.full and world == 1 and not args.no_extras
+        if args.full and world == 1 and not args.no_mbk:
             # BASELINE configs[3] names MiniBatchKMeans(k=1000) as the clusterer of this shape: the same projection through
             # it, once, OUTSIDE the timed steps (`value` stays the metric's tICA + KCenters pipeline)
             from msmbuilder_amd import MiniBatchKMeans
@@ -585,7 +635,7 @@ def main():
                                     "pcie_gen5_x16_GBps": 63.0}
             del host_seqs, mh
 
-        if not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported on rank 0 at N=1 only
             sample = [s.cpu().numpy() for s in seqs[:64]]
             base, oracle, used = cpu_baseline(sample, args.lag, args.components, args.clusters)
             out["cpu_baseline"] = base

@@ -35,7 +35,7 @@ pmc() {  # $1 tag, $2 counters, rest: command
   rm -rf $OUT/tmp_$tag
 }
 B="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-mbk --no-extras"
-python $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt; tail -c 600 $OUT/bench_line.json; echo
+python $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt; tail -c 600 $OUT/bench_line.json; echo
 stats bench $B
 pmc pmc_bench_fetch "FETCH_SIZE" $B
 pmc pmc_bench_write "WRITE_SIZE" $B

@@ -25,7 +25,7 @@ json.dump(d, open(p, "w"), indent=2)
 open(root + "/gpurun_out/r03/traffic.json", "w").write(open(p).read())
 print("traffic.json:", f, w, k["bytes_per_launch"], k["tica_hip_sha16"])
 PY
-timeout 600 python $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt
+timeout 600 python $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt
 python -c "
 import json
 d=json.load(open('$OUT/bench_line.json'))

@@ -38,7 +38,7 @@ pmc() {  # $1 tag, $2 counters, rest: command
 }
 B="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-mbk --no-extras"
 for sec in $SECTIONS; do case $sec in
-bench) timeout 600 python $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt; tail -c 400 $OUT/bench_line.json; echo ;;
+bench) timeout 600 python $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt; tail -c 400 $OUT/bench_line.json; echo ;;
 stats) stats bench $B ;;
 pmc)   pmc pmc_bench_fetch "FETCH_SIZE" $B
        pmc pmc_bench_write "WRITE_SIZE" $B

@@ -74,7 +74,7 @@ open(out + "/traffic.json", "w").write(open(p).read())
 print("traffic.json:", f, w, k["bytes_per_launch"], k["tica_hip_sha16"])
 PY
        ;;
-bench) (cd $ROOT && timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt)
+bench) (cd $ROOT && timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt)
        python -c "
 import json
 d=json.loads(open('$OUT/bench_line.json').read().strip().splitlines()[-1])
