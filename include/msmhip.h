@@ -377,6 +377,9 @@ int msm_kcenters_last_stats(msm_idx_t* out5);
 /* Wide screened passes (round 6: float32 rows, float64 rows of more than 16 features; csrc/distance_wscreen_dev.h), with
  * MSM_KC_STATS=1 in the environment of the fit: out2 = {rows re-evaluated exactly over all screened passes, rows that changed}. */
 int msm_kcenters_last_wide_stats(msm_idx_t* out2);
+/* Batched screened passes of the last k-centers fit (several centres per pass): out1 = {rounds whose threshold list was
+ * unusable, so that the pass applied one centre}; 0 when the fit ran no batches. */
+int msm_kcenters_last_batch_fallbacks(msm_idx_t* out1);
 
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works

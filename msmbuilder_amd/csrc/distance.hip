@@ -416,7 +416,7 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
     DevBuf &dX = pool(PS_X), &dLab = pool(PS_LAB), &dDist = pool(PS_MIN), &dPart = pool(PS_PART), &dIds = pool(PS_IDS),
            &dSum = pool(PS_SUM);
     int nblk = (int)std::min<long long>(ceil_div(n, DT), KC_MAXBLK);
-    if ((rc = dPart.reserve((size_t)2 * nblk * sizeof(KcPartial)))) return rc;
+    if ((rc = dPart.reserve((size_t)2 * nblk * sizeof(KcPartial)))) return rc;   // partials: two arrays nblk0 apart; pass it writes array it & 1 and reads the other
     if ((rc = dIds.reserve((size_t)K * sizeof(msm_idx_t)))) return rc;
     if ((rc = dSum.reserve((size_t)nblk * sizeof(double)))) return rc;
     KcArgs P;
@@ -448,7 +448,7 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
         P.m = m = mp;
     }
     P.vecw = row_vecw<T>(P.X, m, false);
-    const int nblk0 = nblk;   // (the partial buffers hold two arrays of this many entries)
+    const int nblk0 = nblk;   // (the stride of the two partial arrays, whatever grid a pass runs on)
     if (P.vecw == 0 && wide_ok<T>(P.X, P.X, m, false)) P.nblk = nblk = std::min(nblk, wide_grid(n));
     KcPartial* part = dPart.as<KcPartial>();
     const bool screen = sizeof(T) == 8 && mid == M_EUCLIDEAN && P.vecw > 0 && n >= 65536 && K > 8;
@@ -473,8 +473,8 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
         msm_idx_t it = 0;
         for (; it < K && it < KSC_PROBE; ++it) {
             P.it = (int)it;
-            P.prev = part + (size_t)((it + 1) & 1) * nblk;
-            P.next = part + (size_t)(it & 1) * nblk;
+            P.prev = part + (size_t)((it + 1) & 1) * nblk0;
+            P.next = part + (size_t)(it & 1) * nblk0;
             launch_kc<T>(mid, nblk, P);
         }
         const bool use_screen = it < K;
@@ -518,8 +518,8 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
                 while (done < (int)K) {
                     const int group = kcb_group((int)K, done, rounds, (int)it);
                     for (int r = 0; r < group; ++r, ++rounds) {
-                        S.prev = part + (size_t)((it + 1 + rounds) & 1) * nblk;   // partials of the last pass that ran
-                        S.next = part + (size_t)((it + rounds) & 1) * nblk;
+                        S.prev = part + (size_t)((it + 1 + rounds) & 1) * nblk0;   // partials of the last pass that ran
+                        S.next = part + (size_t)((it + rounds) & 1) * nblk0;
                         switch (np) {
 #define MSM_KSC(NP_) case NP_: hipLaunchKernelGGL((kcb_select_kernel<NP_>), dim3(1), dim3(1024), 0, stream(), S, St, (int)K); \
                                hipLaunchKernelGGL((kcenters_batch_pass_kernel<NP_>), dim3(nblk), dim3(DT), 0, stream(), S, St); break;
@@ -539,8 +539,8 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
             }
             for (; it < K; ++it) {
                 S.it = (int)it;
-                S.prev = part + (size_t)((it + 1) & 1) * nblk;
-                S.next = part + (size_t)(it & 1) * nblk;
+                S.prev = part + (size_t)((it + 1) & 1) * nblk0;
+                S.next = part + (size_t)(it & 1) * nblk0;
                 switch (np) {
 #define MSM_KSC(NP_) case NP_: hipLaunchKernelGGL((kcenters_screen_pass_kernel<NP_, fmt>), dim3(nblk), dim3(DT), 0, stream(), S); break;
                     MSM_KSC(1) MSM_KSC(2) MSM_KSC(3) MSM_KSC(4) MSM_KSC(5) MSM_KSC(6) MSM_KSC(7) MSM_KSC(8)
@@ -559,8 +559,8 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
         msm_idx_t it = 0;
         for (; it < K && it < KWS_PROBE; ++it) {
             P.it = (int)it;
-            P.prev = part + (size_t)((it + 1) & 1) * nblk;
-            P.next = part + (size_t)(it & 1) * nblk;
+            P.prev = part + (size_t)((it + 1) & 1) * nblk0;
+            P.next = part + (size_t)(it & 1) * nblk0;
             launch_kc<T>(mid, nblk, P);
         }
         if (it < K) {
@@ -601,8 +601,7 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
             const size_t lds = (size_t)4 * nb4 * sizeof(float) + (size_t)m * sizeof(T);
             const int kr = nb4 <= 4 ? 8 : nb4 <= 16 ? 4 : 2;   // rows per thread (x 4 / 8 / 16 planes per trip: distance_wscreen_dev.h)
             const int gpass = (int)std::min<long long>(ceil_div(n, (long long)kr * DT), nblk0);
-            // (the screened passes write `gpass` partials into arrays `nblk0` apart; the plain passes before them wrote `nblk`
-            //  partials `nblk` apart: the first screened pass reads those)
+            // (the screened passes write `gpass` partials, the plain passes before them `nblk`: S.nblk is what the last pass wrote)
             // Several centres per pass (distance_wbatch_dev.h): as many as fit 64 KiB of LDS beside the pass's own 40 KiB --
             // 16 up to 256 float32 / 170 float64 features, 8 up to twice that, one beyond.  MSM_KC_WBATCH=0: one centre per pass.
             int jmax = 0;
@@ -661,7 +660,7 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
                 while (done < (int)K) {
                     const int group = kcb_group((int)K, done, rounds, it0);
                     for (int r = 0; r < group; ++r, ++rounds) {
-                        S.prev = rounds == 0 ? part + (size_t)((it0 + 1) & 1) * nblk : part + (size_t)((it0 + rounds + 1) & 1) * nblk0;
+                        S.prev = part + (size_t)((it0 + rounds + 1) & 1) * nblk0;
                         S.next = part + (size_t)((it0 + rounds) & 1) * nblk0;
                         S.nblk = rounds == 0 ? nblk : gp2;
                         if (nbsel) hipLaunchKernelGGL((kwb_select_multi_kernel<T>), dim3(nbsel), dim3(DT), ldssel, stream(), S, St, Sy, (int)K, jmax, wcap);
@@ -689,7 +688,7 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
             }
             for (; it < K; ++it) {
                 S.it = (int)it;
-                S.prev = it == KWS_PROBE ? part + (size_t)((it + 1) & 1) * nblk : part + (size_t)((it + 1) & 1) * nblk0;
+                S.prev = part + (size_t)((it + 1) & 1) * nblk0;
                 S.next = part + (size_t)(it & 1) * nblk0;
                 S.nblk = it == KWS_PROBE ? nblk : gpass;
                 if (kr == 8) hipLaunchKernelGGL((kcenters_wscreen_pass_kernel<T, 8, 4>), dim3(gpass), dim3(DT), lds, stream(), S);
@@ -707,8 +706,8 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
     } else
     for (msm_idx_t it = 0; it < K; ++it) {
         P.it = (int)it;
-        P.prev = part + (size_t)((it + 1) & 1) * nblk;
-        P.next = part + (size_t)(it & 1) * nblk;
+        P.prev = part + (size_t)((it + 1) & 1) * nblk0;
+        P.next = part + (size_t)(it & 1) * nblk0;
         launch_kc<T>(mid, nblk, P);
     }
     MSM_HIP_CHECK(hipGetLastError());
@@ -1343,6 +1342,13 @@ int msm_kcenters_last_wide_stats(msm_idx_t* out2)
     if (!out2) return fail(MSM_ERR_INVALID, "msm_kcenters_last_wide_stats: null pointer");
     out2[0] = g_kc_stats.wide_candidates;
     out2[1] = g_kc_stats.wide_updates;
+    return MSM_OK;
+}
+
+int msm_kcenters_last_batch_fallbacks(msm_idx_t* out1)
+{
+    if (!out1) return fail(MSM_ERR_INVALID, "msm_kcenters_last_batch_fallbacks: null pointer");
+    out1[0] = g_kc_stats.batch_fallbacks;
     return MSM_OK;
 }
 

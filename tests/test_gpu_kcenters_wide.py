@@ -4,7 +4,9 @@ scan's bit for bit (the C oracle = kcenters.py:79-102 over libdistance.dist, pin
 adversarial inputs of tests/test_gpu_fullsize.py::test_kcenters_float32_screened_passes: duplicate rows (float32-image ties in
 the argmax), a large common offset, values beyond the float32 range and a NaN (the screen must switch itself off / never
 assign), rows on a shell around the copy's origin (the margin is tight for every row), anisotropic scales, a lattice (masses of
-exactly equal distances), tiny and huge scales; and the same fit with the screen switched off (MSM_KC_WSCREEN=0)."""
+exactly equal distances), tiny and huge scales; and the same fit with the screen switched off (MSM_KC_WSCREEN=0).
+These are input cases at sizes where the passes' grids mostly agree; the sizes where they differ (the wide plain grid full,
+the partial count at its cap, screened grids larger than the plain one) are tests/test_gpu_kcenters_grid.py's."""
 import numpy as np
 import pytest
 
