@@ -10,3 +10,4 @@ from . import libdistance  # noqa: F401
 from . import preprocessing  # noqa: F401
 from .cluster import KCenters, MiniBatchKMeans  # noqa: F401
 from .decomposition import tICA  # noqa: F401
+from .msm import MarkovStateModel  # noqa: F401

@@ -202,4 +202,39 @@ int msm_sygv_top(const double* A, const double* B, msm_idx_t n, msm_idx_t k, dou
     return MSM_OK;
 }
 
+int msm_syev_top(const double* S, msm_idx_t n, msm_idx_t k, double* evals, double* evecs, int on_device)
+{
+    if (!S || !evals || !evecs) return fail(MSM_ERR_INVALID, "msm_syev_top: null pointer");
+    if (n < 1 || n > 32768 || k < 1 || k > n) return fail(MSM_ERR_INVALID, "msm_syev_top: need 1 <= k <= n <= 32768");
+    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
+    int rc;
+    const size_t nn = (size_t)n * n;
+    DevBuf &dA = pool(PS_X), &dW = pool(PS_W), &dO = pool(PS_OUT);
+    if ((rc = dA.reserve(nn * sizeof(double)))) return rc;
+    if ((rc = dW.reserve((size_t)2 * n * sizeof(double) + 16))) return rc;
+    if ((rc = dO.reserve(((size_t)k * n + k) * sizeof(double)))) return rc;
+    if (on_device) {
+        MSM_HIP_CHECK(hipMemcpyAsync(dA.p, S, nn * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+    } else if ((rc = h2d_bulk(dA.p, S, nn * sizeof(double)))) {
+        return rc;
+    }
+    double* D = dW.as<double>();
+    double* E = D + n;
+    int* info = reinterpret_cast<int*>(E + n);
+    if ((rc = syevd_device(dA.as<double>(), (int)n, D, E, info))) return rc;   // symmetric: row-major == column-major
+    double* ovecs = dO.as<double>();
+    double* ovals = ovecs + (size_t)k * n;
+    hipLaunchKernelGGL(top_pairs_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, stream(),
+                       dA.as<double>(), D, (int)n, (int)k, ovecs, ovals);
+    MSM_HIP_CHECK(hipGetLastError());
+    int hinfo = 0;
+    MSM_HIP_CHECK(hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, stream()));
+    const hipMemcpyKind out = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    MSM_HIP_CHECK(hipMemcpyAsync(evecs, ovecs, (size_t)k * n * sizeof(double), out, stream()));
+    MSM_HIP_CHECK(hipMemcpyAsync(evals, ovals, (size_t)k * sizeof(double), out, stream()));
+    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    if (hinfo != 0) return fail(MSM_ERR_INVALID, "eigenvalue iteration did not converge (info = %d)", hinfo);
+    return MSM_OK;
+}
+
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Post-clustering counting step: ``_transition_counts`` as in ``msmbuilder.msm``."""
+"""Post-clustering MSM step: ``_transition_counts`` and ``MarkovStateModel`` as in ``msmbuilder.msm``."""
 from .core import _transition_counts  # noqa: F401
+from .msm import MarkovStateModel  # noqa: F401
 
-__all__ = ['_transition_counts']
+__all__ = ['_transition_counts', 'MarkovStateModel']
