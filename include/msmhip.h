@@ -561,17 +561,22 @@ int msm_sygv_top(const double* A, const double* B, msm_idx_t n, msm_idx_t k, dou
  *   launch (msm_mle.hip).  Outputs (host): T (n x n), pi (n), optionally S (n x n, NULL = skip) =
  *   D^-1/2 X D^-1/2 with X = diag(x_rs) T symmetric and D = diag(x_rs): symmetric, T's eigenvalues.
  *   info (host, 4 doubles): iterations, converged (1.0), last relative step max|g(x) - x| / max g(x),
- *   KKT residual max|g(pi) - pi| / max pi.  Stops at a step below 1e-14 or after max_iter iterations.
+ *   KKT residual max|g(pi) - pi| / max pi.  Stops at a step below 1e-14 with every state's own relative step
+ *   |g_i(x) - x_i| / g_i(x) below 1e-13, or after max_iter iterations.
  *   MSM_ERR_INVALID with the reference's messages and codes: "Row-sums of C must be positive. Error code=-1" (a
  *   row sum of C or C + C^T not positive, prefixed to "Domain error. C must be positive." when there are also
  *   negative entries), "Domain error. C must be positive. Error code=-2" (negative entries, row sums positive),
- *   "Likelihood not converged. Error code=-3".  1 <= n <= 16384 (the pattern is built densely on the host).
+ *   "Likelihood not converged. Error code=-3"; NaN or infinite entries are the -2 domain error.  1 <= n <= 16384 (the pattern is built densely on the host).
  *   Sparse (sliced ELL of the pattern of C + C^T) when prior == 0; dense when prior != 0 (every entry is filled)
  *   or with MSM_MLE_DENSE=1.
+ * msm_mle_last_stats: how the last msm_transmat_mle of this process stepped (out3: mixed steps accepted, mixed
+ *   steps rejected because an entry was not positive, mixing solves rejected as singular or non-finite; each
+ *   rejection took the plain step x <- g(x) / sum g(x)).  For the tests of those branches.
  * msm_syev_top: the k largest eigenvalues (descending, evals[k]) and their eigenvectors (evecs[j * n + i],
  *   orthonormal) of the symmetric n x n S; rocSOLVER dsyevd, as msm_sygv_top.  on_device as msm_sygv_top. */
 int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_iter, double* T, double* pi, double* S,
                      double* info);
+int msm_mle_last_stats(msm_idx_t* out3);
 int msm_syev_top(const double* S, msm_idx_t n, msm_idx_t k, double* evals, double* evecs, int on_device);
 
 #ifdef __cplusplus

@@ -129,6 +129,7 @@ def _declare(lib):
     f("msm_npy_loader_wait", C.c_int, _p, _i64)
     f("msm_npy_loader_destroy", C.c_int, _p)
     f("msm_sygv_top", C.c_int, _p, _p, _i64, _i64, _p, _p, C.c_int)
+    f("msm_mle_last_stats", C.c_int, _i64p)
     f("msm_syev_top", C.c_int, _p, _i64, _i64, _p, _p, C.c_int)
     f("msm_transmat_mle", C.c_int, _p, _i64, C.c_double, _i64, _p, _p, _p, _p)
     f("msm_colstats", C.c_int, C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _i64, C.c_int, _p, C.POINTER(C.c_int))

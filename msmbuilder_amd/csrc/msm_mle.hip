@@ -8,7 +8,11 @@
 // the last MLE_AM iterates.  The m x m least-squares problem of the mixing is solved by one thread from an
 // incrementally updated Gram matrix (normal equations, no ridge: a ridge biases the mixing once the residuals are
 // small, and the iteration stalls -- 1e-10 relative stalled a 3,000-state banded chain near 1e-10); a mixed step
-// with any x_i <= 0, or a singular or non-finite solve, falls back to the plain step.  Stopping rule: max|g(x) - x| / max g(x) < tol.
+// with any x_i <= 0, or a singular or non-finite solve, falls back to the plain step.  Stopping rule:
+// max|g(x) - x| / max g(x) < tol AND max_i |g_i(x) - x_i| / g_i(x) < MLE_STATE_TOL.  The first alone leaves a state of
+// population p converged only to tol / p of itself (measured: 1e-4 relative on the rarest state of a ten-decade range, and
+// T, formed from x, 4e-12 off its closed form in pi = g(x) / sum g on a 6,145-state hub); the second is 1e-13, above the
+// rounding of a K-term row sum (~sqrt(K) eps <= 1.4e-14) and below what T's closed form needs.
 // On exit X_ij = Cs_ij / (d_i + d_j), x_rs = row sums of X, T = X / x_rs, pi = x_rs / sum(x_rs), and the
 // symmetric S = D^-1/2 X D^-1/2 (D = diag(x_rs)), which has T's eigenvalues.
 //
@@ -36,6 +40,7 @@ constexpr int MLE_WAVES = MLE_T / 64;
 constexpr int MLE_AM = 6;           // Anderson depth
 constexpr int MLE_LDS_K = 6144;     // d lives in LDS up to this many states (48 KiB), in global memory beyond
 constexpr int MLE_MAX_K = 16384;
+constexpr double MLE_STATE_TOL = 1e-13;   // per-state relative residual at convergence
 
 struct MleArgs {
     int K;
@@ -52,7 +57,8 @@ struct MleArgs {
     double* dF;             // [MLE_AM][K] residual differences
     double* dG;             // [MLE_AM][K] image differences
     double* pi;             // [K] out
-    double* info;           // out: iterations, converged (0/1), last step, KKT residual at pi
+    double* info;           // out: iterations, converged (0/1), last step, KKT residual at pi; then the counts of mixed
+                            // steps accepted, mixed steps rejected as not positive, solves rejected (singular / non-finite)
     int max_iter;
     double tol;
 };
@@ -164,23 +170,26 @@ __global__ __launch_bounds__(MLE_T) void mle_solve_kernel(MleArgs A)
         for (int i = tid; i < K; i += MLE_T) A.x[i] *= inv;
     }
     int it = 0, mk = 0, slot = 0, conv = 0;
+    int n_mixed = 0, n_nonpos = 0, n_sing = 0;   // uniform over the workgroup: they follow shared decisions
     double step = INFINITY, sg = 0.0;
     for (;; ++it) {
         for (int i = tid; i < K; i += MLE_T) d[i] = A.c[i] / A.x[i];
         __syncthreads();
-        double mm[2] = {0.0, 0.0}, ss[1] = {0.0};
+        double mm[3] = {0.0, 0.0, 0.0}, ss[1] = {0.0};
         for (int i = tid; i < K; i += MLE_T) {
             const double gi = row_g(A, d, i, d[i]);
             A.g[i] = gi;
             ss[0] += gi;
             mm[0] = fmax(mm[0], gi);
             mm[1] = fmax(mm[1], fabs(gi - A.x[i]));
+            mm[2] = fmax(mm[2], fabs(gi - A.x[i]) / gi);
         }
-        block_reduce<2, true>(mm, red, tot);
+        block_reduce<3, true>(mm, red, tot);
         step = tot[1] / tot[0];
+        const double state_step = tot[2];
         block_reduce<1, false>(ss, red, tot);
         sg = tot[0];
-        if (step < A.tol) {
+        if (step < A.tol && state_step < MLE_STATE_TOL) {
             conv = 1;
             break;
         }
@@ -222,6 +231,7 @@ __global__ __launch_bounds__(MLE_T) void mle_solve_kernel(MleArgs A)
         }
         __syncthreads();
         int use = mix;
+        if (mn > 0 && !use) ++n_sing;
         if (use) {   // x_new = G - dG gam; accepted only if every entry is positive (and finite)
             double acc[2] = {0.0, 0.0};
             for (int i = tid; i < K; i += MLE_T) {
@@ -236,6 +246,7 @@ __global__ __launch_bounds__(MLE_T) void mle_solve_kernel(MleArgs A)
             const double s = tot[0];
             if (use)
                 for (int i = tid; i < K; i += MLE_T) A.x[i] = A.g[i] / s;
+            use ? ++n_mixed : ++n_nonpos;
         }
         if (!use)
             for (int i = tid; i < K; i += MLE_T) A.x[i] = A.Gp[i];
@@ -259,6 +270,9 @@ __global__ __launch_bounds__(MLE_T) void mle_solve_kernel(MleArgs A)
         A.info[1] = (double)conv;
         A.info[2] = step;
         A.info[3] = tot[1] / tot[0];
+        A.info[4] = (double)n_mixed;
+        A.info[5] = (double)n_nonpos;
+        A.info[6] = (double)n_sing;
     }
 }
 
@@ -294,6 +308,8 @@ __global__ void mle_out_dense_kernel(MleArgs A, double* __restrict__ T, double* 
     }
 }
 
+int64_t g_mle_stats[3] = {0, 0, 0};   // the last solve's info[4 .. 7)
+
 }  // namespace
 }  // namespace msm
 
@@ -312,12 +328,13 @@ int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_i
     const size_t KK = (size_t)K * K;
     // row sums and the domain checks (the reference's error codes and messages)
     std::vector<double> c(K, 0.0), colsum(K, 0.0);
-    bool negative = false, zero_row = false;
+    bool negative = false, zero_row = false, nonfinite = false;
     for (int i = 0; i < K; ++i) {
         double s = 0.0;
         for (int j = 0; j < K; ++j) {
             const double v = C[(size_t)i * K + j] + prior;
             negative |= v < 0.0;
+            nonfinite |= !std::isfinite(v);
             s += v;
             colsum[j] += v;
         }
@@ -336,6 +353,9 @@ int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_i
             for (int i = i0; i < std::min(K, i0 + 64); ++i)
                 for (int j = j0; j < std::min(K, j0 + 64); ++j)
                     cs[(size_t)i * K + j] = (C[(size_t)i * K + j] + prior) + (C[(size_t)j * K + i] + prior);
+    // NaN or infinite counts: the reference's solver returns -2 on them (its sweep fails), and its wrapper has no text of
+    // its own for that; they are a domain error like the negative entries that share the code
+    if (nonfinite) return fail(MSM_ERR_INVALID, "Domain error. C must be positive. Error code=-2");
     if (rows_bad || negative) {
         std::string msg = rows_bad ? " Error code=-1" : " Error code=-2";
         if (negative) msg = "Domain error. C must be positive." + msg;
@@ -411,10 +431,11 @@ int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_i
     MSM_HIP_CHECK(hipMemcpyAsync(w, c.data(), K * sizeof(double), hipMemcpyHostToDevice, stream()));
     hipLaunchKernelGGL(mle_solve_kernel, dim3(1), dim3(MLE_T), 0, stream(), A);
     MSM_HIP_CHECK(hipGetLastError());
-    double hinfo[4];
+    double hinfo[7];
     MSM_HIP_CHECK(hipMemcpyAsync(hinfo, A.info, sizeof(hinfo), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
     for (int q = 0; q < 4; ++q) info[q] = hinfo[q];
+    for (int q = 0; q < 3; ++q) g_mle_stats[q] = (int64_t)hinfo[4 + q];
     if (hinfo[1] != 1.0) return fail(MSM_ERR_INVALID, "Likelihood not converged. Error code=-3");
     double* dT = dO.as<double>();
     double* dS = dT + KK;
@@ -430,6 +451,13 @@ int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_i
     if ((rc = d2h_bulk(T, dT, KK * sizeof(double)))) return rc;
     if (S && (rc = d2h_bulk(S, dS, KK * sizeof(double)))) return rc;
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    return MSM_OK;
+}
+
+int msm_mle_last_stats(msm_idx_t* out3)
+{
+    if (!out3) return fail(MSM_ERR_INVALID, "msm_mle_last_stats: null pointer");
+    for (int q = 0; q < 3; ++q) out3[q] = g_mle_stats[q];
     return MSM_OK;
 }
 

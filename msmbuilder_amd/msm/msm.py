@@ -236,6 +236,8 @@ class MarkovStateModel(BaseEstimator):
                            self.n_states_ - 1)
         k = n_timescales + 1
         if self._sym is not None and k >= 1:
+            if not np.all(np.isfinite(self._sym)):   # 'transpose' with a zero-count state: scipy.linalg.eig's refusal
+                raise ValueError("array must not contain infs or NaNs")
             u, y = _symmetric_top(self._sym, k)
             root = np.sqrt(self.populations_)
             lv = y * root[:, None]

@@ -36,9 +36,12 @@ def kkt_residual(C, pi):
     return np.abs(g_map(C + C.T, C.sum(1), pi) - pi).max() / pi.max()
 
 
-def mle_numpy(C, tol=1e-14, m=6, max_iter=100000):
+def mle_numpy(C, tol=1e-14, m=6, max_iter=100000, stats=None):
     """Reversible MLE of the counts C: (T, pi, iterations).  Fixed point x = g(x) on the simplex, Anderson mixing
-    over m iterates (normal equations, no ridge), plain step whenever a mixed one is not positive."""
+    over m iterates (normal equations, no ridge), plain step whenever a mixed one is not positive.  ``stats`` (a dict)
+    receives the counts of mixed steps accepted, rejected as non-positive, and solves rejected as singular."""
+    if stats is not None:
+        stats.update(accepted=0, nonpositive=0, singular=0)
     C = np.asarray(C, dtype=float)
     if C.shape[0] == 0:
         return np.zeros((0, 0)), np.zeros(0), 0
@@ -77,10 +80,16 @@ def mle_numpy(C, tol=1e-14, m=6, max_iter=100000):
             try:
                 gam = np.linalg.solve(M, A.T @ F)
             except np.linalg.LinAlgError:
+                if stats is not None:
+                    stats['singular'] += 1
                 continue
             xn = G - np.array(dG).T @ gam
             if np.all(xn > 0) and np.all(np.isfinite(xn)):
                 x = xn / xn.sum()
+                if stats is not None:
+                    stats['accepted'] += 1
+            elif stats is not None:
+                stats['singular' if not np.all(np.isfinite(gam)) else 'nonpositive'] += 1
     d = c / x
     X = Cs / (d[:, None] + d[None, :])
     rs = X.sum(1)
@@ -125,6 +134,89 @@ def well_counts(n_states, seed, stay=0.98, width=3, wells=4):
     return C
 
 
+def ring_links(K, deg, seed):
+    """Well-mixed asymmetric counts: a ring (self and +-1, poisson(20) + 1 each) plus `deg` random links per row
+    (poisson(3) each)."""
+    rs = np.random.RandomState(seed)
+    C = np.zeros((K, K))
+    idx = np.arange(K)
+    for off in (-1, 0, 1):
+        np.add.at(C, (idx, (idx + off) % K), rs.poisson(20, K) + 1.0)
+    for _ in range(deg):
+        np.add.at(C, (idx, rs.randint(0, K, K)), rs.poisson(3, K).astype(float))
+    return C
+
+
+def hub(K, seed):
+    """ring_links plus one state linked to every other in both directions: its row of the pattern has K entries
+    (its 64-row slice is padded to that width) while the others keep about 5."""
+    rs = np.random.RandomState(seed + 1000)
+    C = ring_links(K, 3, seed)
+    h = int(rs.randint(K))
+    C[h, :] += rs.poisson(2, K) + 1.0
+    C[:, h] += rs.poisson(2, K) + 1.0
+    return C
+
+
+def ragged(K, seed):
+    """Row lengths between 2 and 200 that differ widely between and inside 64-row slices: runs of 1..96 rows (not
+    aligned to the slices) draw a ceiling from {2, .., 200}, each row of a run a length up to that ceiling, and the
+    symmetric pattern with about those row lengths is a random pairing of that many stubs per row (duplicate pairs
+    merge); a thin ring keeps the chain irreducible."""
+    rs = np.random.RandomState(seed)
+    top = min(200, K - 1)
+    L = np.empty(K, np.int64)
+    i = 0
+    while i < K:
+        run = int(rs.randint(1, 97))
+        ceil_ = int(rs.randint(2, top + 1))
+        L[i:i + run] = rs.randint(2, ceil_ + 1, len(L[i:i + run]))
+        i += run
+    stubs = rs.permutation(np.repeat(np.arange(K), L))
+    a, b = stubs[0:len(stubs) // 2 * 2:2], stubs[1:len(stubs) // 2 * 2:2]
+    C = np.zeros((K, K))
+    np.add.at(C, (a, b), rs.poisson(5, len(a)) + 1.0)
+    np.add.at(C, (b, a), rs.poisson(5, len(a)) + 1.0)
+    idx = np.arange(K)
+    np.add.at(C, (idx, (idx + 1) % K), rs.poisson(2, K) + 1.0)
+    np.add.at(C, ((idx + 1) % K, idx), rs.poisson(2, K) + 1.0)
+    return C
+
+
+def wide_range(K, seed, decades=10.0):
+    """Fractional asymmetric counts of a Metropolis-like walk (jumps of up to 2 states) on a 1-D slope whose
+    equilibrium populations span `decades` decades: C_ij = N pi_i min(1, pi_j / pi_i) (1 + noise)."""
+    rs = np.random.RandomState(seed)
+    logp = -np.log(10.0) * decades * np.arange(K) / max(K - 1, 1)
+    C = np.zeros((K, K))
+    for i in range(K):
+        for j in range(max(0, i - 2), min(K, i + 3)):
+            C[i, j] = 1e6 * np.exp(logp[i] + min(0.0, logp[j] - logp[i])) * (1.0 + 0.3 * rs.rand())
+    return C
+
+
+def star(K, seed):
+    """One centre with few counts out to and many counts in from every other state, and self counts over six decades:
+    the start (row sums of C + C^T) is far from the solution, and mle_numpy rejects mixed steps as non-positive."""
+    rs = np.random.RandomState(seed)
+    C = np.zeros((K, K))
+    C[0, 1:] = rs.poisson(5, K - 1) + 1
+    C[1:, 0] = rs.poisson(500, K - 1) + 1
+    C[np.arange(K), np.arange(K)] = rs.poisson(1000, K) * rs.rand(K) ** 4 + 1e-3
+    return C
+
+
+def blocks(sizes, seed):
+    """Block-diagonal (reducible) counts: one ring_links block per size; a block of size 1 is a self-looping state."""
+    K = int(np.sum(sizes))
+    C = np.zeros((K, K))
+    o = 0
+    for b, n in enumerate(sizes):
+        C[o:o + n, o:o + n] = ring_links(n, 2, seed + b)
+        o += n
+    return C
+
+
 def cases():
     """name -> (sequences, params, score_sequences)."""
     rs = np.random.RandomState(42)
@@ -153,6 +245,11 @@ def cases():
     b = metastable_labels(rs, 2000, 3, 0.9) + 10
     out['disconnected'] = ([a, b], dict(lag_time=1, n_timescales=2), None)
     out['meta299'] = ([well_chain(299, 400000, 1)], dict(lag_time=1, n_timescales=10, verbose=False), None)
+    # a state without counts (its only sequence is shorter than the lag) kept by ergodic_cutoff='off': the 'transpose'
+    # estimator divides by its zero row sum, and the reference's eigensolver refuses the non-finite matrix
+    rs2 = np.random.RandomState(77)
+    out['transpose_zero'] = ([metastable_labels(rs2, 3000, 5, 0.9), np.array([9])],
+                             dict(lag_time=2, reversible_type='transpose', ergodic_cutoff='off'), None)
     return out
 
 
@@ -211,6 +308,12 @@ def main():
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             m = MSM(**p).fit(seqs)
+            try:
+                m.eigenvalues_
+            except ValueError as e:   # the fit stands, the eigensystem is refused: the message is the fixture
+                eig_error = str(e)
+            else:
+                eig_error = None
         g[name + '_countsmat'] = m.countsmat_
         keys = list(m.mapping_.keys())
         g[name + '_keys'] = np.array(keys)
@@ -219,6 +322,10 @@ def main():
         g[name + '_percent'] = np.float64(m.percent_retained_)
         g[name + '_transmat'] = m.transmat_
         g[name + '_populations'] = m.populations_
+        if eig_error is not None:
+            g[name + '_eig_error'] = np.array(eig_error)
+            print(name, m.n_states_, m.percent_retained_, 'eigensystem:', eig_error)
+            continue
         g[name + '_eigenvalues'] = np.real(m.eigenvalues_)
         g[name + '_lv'] = np.real(m.left_eigenvectors_)
         g[name + '_rv'] = np.real(m.right_eigenvectors_)

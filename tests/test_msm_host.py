@@ -64,7 +64,7 @@ def test_trimming_verbose_line(capsys):
 def test_cabi_symbols():
     from msmbuilder_amd import _lib
     L = _lib.lib()
-    for name in ("msm_transmat_mle", "msm_syev_top"):
+    for name in ("msm_transmat_mle", "msm_mle_last_stats", "msm_syev_top"):
         assert hasattr(L, name)
 
 
