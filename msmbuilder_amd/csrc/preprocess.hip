@@ -93,7 +93,7 @@ __global__ __launch_bounds__(PNT) void colstats_kernel(ScanArgs P)
                 const global_ptr<T> X = as_global<T>(ch.base);
                 const bool al = vec && ((((uintptr_t)ch.base) & 15) == 0);
                 // One chunk (<= SCAN_ROWS rows, 1 / rl of them this thread's) per column as SHIFTED sums
-                // s1 = sum (x - K), s2 = sum (x - K)^2 in float64, K = the running mean (first chunk: the first value):
+                // s1 = sum (x - K), s2 = sum (x - K)^2 in float64, K = the running mean (nothing seen yet: the first finite value):
                 // 4 float64 operations per element and one division per chunk, where the first version (two-pass
                 // batches of 8 rows, one Chan merge with two divisions per batch) was VALU-bound at 2.7 TB/s.
                 // x - K is rounded once (float64); the cancellation in s2 - s1^2/n costs at most
@@ -125,9 +125,18 @@ __global__ __launch_bounds__(PNT) void colstats_kernel(ScanArgs P)
                     }
 #pragma unroll
                     for (int e = 0; e < CW; ++e) {
-                        if (k0 == tr && run[e].n == 0.0) {  // nothing seen yet: shift by the first finite value
-                            const T x0 = v[0][e];
-                            K[e] = (x0 == x0 && x0 != (T)INFINITY && x0 != (T)-INFINITY) ? (double)x0 : 0.0;
+                        if (cnt[e] == 0 && run[e].n == 0.0) {
+                            // nothing summed yet (s1 = s2 = 0, so K is free): shift by the first finite value of this
+                            // batch.  Taking only the thread's very first value left K = 0 when that one was NaN, and
+                            // raw sums lose (mean / std)^2 * eps of M2 (5e-5 at an offset of 1e6 std).  Rows past the
+                            // chunk's end are clamped copies of its last row: as good a shift as any.
+                            double k = 0.0;
+#pragma unroll
+                            for (int u = RU - 1; u >= 0; --u) {
+                                const T x0 = v[u][e];
+                                if (x0 == x0 && x0 != (T)INFINITY && x0 != (T)-INFINITY) k = (double)x0;
+                            }
+                            K[e] = k;
                         }
 #pragma unroll
                         for (int u = 0; u < RU; ++u) {

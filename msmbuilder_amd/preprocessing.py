@@ -184,7 +184,7 @@ class StandardScaler(_MultiSequenceScaler):
         if not self.with_mean and not self.with_std:
             self.mean_, self.var_, self.scale_ = None, None, None
             return
-        self.mean_ = mean.copy()
+        self.mean_ = np.where(n > 0, mean, np.nan)      # a column without a single value: 0 / 0, as in scikit-learn
         if self.with_std:
             with np.errstate(invalid="ignore", divide="ignore"):
                 self.var_ = m2 / n
