@@ -393,6 +393,13 @@ int msm_kmeans_label_f32(const float* X, msm_idx_t n, msm_idx_t m, const float* 
                          msm_idx_t K, int32_t* labels, double* inertia, int on_device);
 int msm_kmeans_label_f64(const double* X, msm_idx_t n, msm_idx_t m, const double* centers,
                          msm_idx_t K, int32_t* labels, double* inertia, int on_device);
+/* What a labelling call of this shape launches -- the library's one dispatch, for tests to ask (pure: works with no device
+ * visible).  handle_entry: msm_mbk_label / _step / _run* (else the stateless msm_kmeans_label_* / msm_mbk_step_*); aligned:
+ * rows and centres start on 16-byte boundaries; gathered: rows are read through an index list.  MSM_LABEL_XCD is read per
+ * call.  Out: *kernel (MSM_KM_*), *nsplit centre splits (1: none) of *span centres each. */
+enum { MSM_KM_SCALAR = 0, MSM_KM_V4 = 1, MSM_KM_V4_XCD = 2, MSM_KM_LABEL64 = 3, MSM_KM_SMALL = 4, MSM_KM_F64 = 5 };
+int msm_kmeans_label_plan(msm_idx_t n, msm_idx_t m, msm_idx_t K, int f64, int handle_entry, int want_inertia, int aligned,
+                          int gathered, int* kernel, int* nsplit, msm_idx_t* span);
 /* k-means++ seeds (scikit-learn `_kmeans_plusplus`, sklearn/cluster/_kmeans.py:163-259; reached from
  * msmbuilder/cluster/__init__.py:67-69) of the n x F rows X (host or device per on_device): centre 0 = row
  * `first`, then K - 1 rounds of L candidates drawn by inverse-CDF sampling of the current squared distances with the

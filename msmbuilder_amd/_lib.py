@@ -155,6 +155,8 @@ def _declare(lib):
         f("msm_kmeans_label_" + sfx, C.c_int, _p, _i64, _i64, _p, _i64, _p, _f64p, C.c_int)
         f("msm_kmeans_plusplus_" + sfx, C.c_int, _p, _i64, _i64, _i64, _i64, _p, C.c_int, _p, _p, C.c_int)
         f("msm_mbk_step_" + sfx, C.c_int, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _f64p, _p, _p, C.c_int, C.c_int)
+    f("msm_kmeans_label_plan", C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+      C.POINTER(C.c_int), C.POINTER(C.c_int64))
     f("msm_mbk_create", C.c_int, C.POINTER(_p), _i64, _i64)
     f("msm_mbk_create_f64", C.c_int, C.POINTER(_p), _i64, _i64)
     f("msm_mbk_is_f64", C.c_int, _p)

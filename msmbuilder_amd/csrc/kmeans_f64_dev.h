@@ -1,10 +1,10 @@
 // kmeans_f64_dev.h -- kmeans_label_f64_kernel: nearest-centre labelling of float64 rows on the fp64 matrix pipe.
-// (included by kmeans.hip; also declares KmArgsT, the argument block shared by the fp32 and fp64 kernels)
+// (included by kmeans.hip; KmArgsT, the argument block shared with the fp32 kernels, is in kmeans_common_dev.h)
 //
-// Why it exists (round 6): msmbuilder.cluster.MiniBatchKMeans is scikit-learn's estimator
-// (/root/reference/msmbuilder/cluster/__init__.py:67-69), scikit-learn keeps float64 input in float64 (labels from a dgemm,
+// Why it exists: msmbuilder.cluster.MiniBatchKMeans is scikit-learn's estimator
+// (msmbuilder/cluster/__init__.py:67-69), scikit-learn keeps float64 input in float64 (labels from a dgemm,
 // float64 centres and counts), and the reference pipeline feeds it the float64 output of tICA.transform
-// (decomposition/tica.py:329-352).  Rounds 1-5 narrowed such input to fp32.  This kernel is the float64 twin of
+// (decomposition/tica.py:329-352).  This kernel is the float64 twin of
 // kmeans_label_kernel:
 //   label_i = argmin_j ( ||c_j||^2 - 2 x_i . c_j )   in float64, first minimum wins
 // x.c on v_mfma_f64_16x16x4_f64 (64 cycles per 2,048 flop and SIMD: 78.6 TF), one workgroup (2 x 2 waves) per 128 rows x 128
@@ -19,30 +19,9 @@
 // (centres split over blockIdx.y so that the chip is filled; candidates merged by the inertia / reduce kernel), the
 // final labelling pass, wide rows.
 #pragma once
-#include "common.h"
+#include "kmeans_common_dev.h"
 
 namespace msm {
-
-constexpr int KNT = 256;   // threads per workgroup of every k-means kernel
-
-template <typename T>   // T = float (fp32 MFMA labelling) or double (fp64 MFMA labelling: scikit-learn keeps float64 input in float64)
-struct KmArgsT {
-    const T* X;             // [n, m] (or gathered batch)
-    const msm_idx_t* rows;  // optional row gather (batch indices), else nullptr
-    long long n, m, K;
-    const T* C;             // device [K, m]
-    const T* cnorm;         // device [K]
-    int32_t* labels;        // [n]
-    // centre-split launch (small batches): blockIdx.y owns centre tiles [y*jspan, (y+1)*jspan) and
-    // writes its (min value, index) candidates to pv/pi [gridDim.y][n]; a reduce kernel finishes
-    long long jspan;        // 0 = all centres in one workgroup
-    int xcd_ns;             // > 0 (kmeans_label_v4_kernel, large n): a 1-D grid of ceil(rowblocks / 8) x 8 x xcd_ns workgroups in
-                            // which the xcd_ns centre splits of a row block are CONSECUTIVE workgroups of one XCD (see the kernel)
-    T* pv;
-    int* pi;
-    const int* stop;        // optional device flag: non-zero -> the launch does nothing (msm_mbk_run: steps queued
-                            // behind the one at which the convergence criterion fired)
-};
 
 constexpr int DKR = 128;   // rows per workgroup
 constexpr int DKC = 128;   // centres per tile
@@ -194,19 +173,7 @@ __global__ __launch_bounds__(KNT, 2) void kmeans_label_f64_kernel(KmArgsT<double
     __syncthreads();
     if (tid < DKR) {
         const long long i = row0 + tid;
-        if (i < P.n) {
-            const double v0 = redv[tid], v1 = redv[DKR + tid];
-            const int i0 = redi[tid], i1 = redi[DKR + tid];
-            const bool second = (v1 < v0 || (v1 == v0 && i1 < i0));
-            int lab = second ? i1 : i0;
-            if (P.jspan) {
-                P.pv[(long long)split * P.n + i] = second ? v1 : v0;
-                P.pi[(long long)split * P.n + i] = lab;
-            } else {
-                if (lab == 0x7fffffff) lab = 0;  // all-NaN row: sklearn's argmin returns 0
-                P.labels[i] = lab;
-            }
-        }
+        if (i < P.n) km_write_row<double>(P, i, redv[tid], redv[DKR + tid], redi[tid], redi[DKR + tid], split);
     }
 }
 

@@ -1,4 +1,4 @@
-"""Every launch path of the k-means labelling code (csrc/kmeans.hip, kmeans_f64_dev.h) against an exact float64 argmin.
+"""Every launch path of the k-means labelling code (csrc/kmeans.hip, kmeans_*_dev.h) against an exact float64 argmin.
 
 The reference and the acceptance rule live in tests/kmeans_label_ref.py (plain numpy, by direct difference): a label that
 differs from the exact one passes only inside the derived forward-error bound of the GEMM form, never between bit-identical
@@ -15,8 +15,8 @@ Planted in every case (``_case``):
     (K = 129: the tile pair; K = 257 in two float64 splits: the split pair).  Those shapes run a second time as variant
     "last" without that pair, so that a dropped one-centre tail tile is caught there.
 
-Which case reaches which seam (the library does not report the path it took; ``launch_plan`` restates the dispatch of
-km_launch_label / km_xcd_splits / km_small_splits / mbk_label_f32 and test_kmeans_label_rule.py pins this table against it):
+Which case reaches which seam (``launch_plan`` is an independent restatement of the dispatch, the library's km_plan;
+test_kmeans_label_rule.py pins this table against both and holds km_plan, through msm_kmeans_label_plan, to launch_plan):
   * kmeans_label_kernel (m % 4 != 0): (129,1,2) one feature, (257,31,129) partial K-step + one-centre tail tile,
     (300,33,257) one full K-step + remainder 1, (385,130,130) four full steps + remainder 2, two-centre tail tile;
     and the misaligned device view (m = 64, base 4 bytes into its allocation): the 16-byte kernel must be refused.
@@ -60,7 +60,7 @@ def _cdiv(a, b):
 
 
 def _small_splits(n, K):
-    """km_small_splits: (number of centre splits, centres per split)."""
+    """Centre splits of a small batch: (number of centre splits, centres per split)."""
     rowblocks, ctiles = _cdiv(n, KR), _cdiv(K, KCT)
     ns = min(ctiles, max(1, 512 // rowblocks)) if rowblocks < 256 and ctiles > 1 else 1
     tiles_per = _cdiv(ctiles, ns)
@@ -68,7 +68,7 @@ def _small_splits(n, K):
 
 
 def _xcd_splits(n, m, K, tiles_per=4, aligned=True):
-    """km_xcd_splits / km_launch_label_xcd: (number of centre splits or 0, centres per split)."""
+    """The XCD-grouped launch: (number of centre splits or 0, centres per split)."""
     rowblocks, ctiles = _cdiv(n, KR), _cdiv(K, KCT)
     if tiles_per <= 0 or not aligned or m % 4 or m < 64 or ctiles < 2 or ctiles > 16 or rowblocks < 512:
         return 0, 0
@@ -77,7 +77,7 @@ def _xcd_splits(n, m, K, tiles_per=4, aligned=True):
 
 
 def launch_plan(n, m, K, f64=False, entry="label", inertia=True, xcd_tiles=4, aligned=True):
-    """(kernel, centre splits, centres per split) of a labelling call, restated from the dispatch in kmeans.hip."""
+    """(kernel, centre splits, centres per split) of a labelling call, restated from the dispatch in kmeans.hip (km_plan)."""
     v4 = "v4" if (m % 4 == 0 and aligned) else "scalar"
     if f64:
         ns, span = _small_splits(n, K)

@@ -1,6 +1,9 @@
 """CPU tier of the k-means labelling parity rule (tests/kmeans_label_ref.py): the exact reference is what it says it is,
-the rule rejects what it must, it stays decidable on the data the GPU tests use, and the cases of
-tests/test_gpu_kmeans_label_paths.py sit on the seams its docstring names."""
+the rule rejects what it must, it stays decidable on the data the GPU tests use, the cases of
+tests/test_gpu_kmeans_label_paths.py sit on the seams its docstring names, and the library's own dispatch (km_plan,
+asked through msm_kmeans_label_plan: needs no device) is the one that module restates in launch_plan."""
+import ctypes
+import itertools
 import os
 import sys
 
@@ -104,12 +107,53 @@ def test_offset_shift_is_the_largest_that_stays_decidable():
     assert R.OFFSET_SHIFT == 3.0
 
 
-def test_cases_sit_on_their_seams():
+KERNEL_NAMES = ("scalar", "v4", "v4-xcd", "label64", "small", "f64")      # MSM_KM_* of include/msmhip.h, in order
+
+
+def library_plan(n, m, K, f64=False, entry="label", inertia=True, aligned=True, gathered=False):
+    """(kernel, centre splits, centres per split) as the library's km_plan decides them; MSM_LABEL_XCD is read per call."""
+    from msmbuilder_amd import _lib
+    kernel, ns, span = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int64(-1)
+    _lib.check(_lib.lib().msm_kmeans_label_plan(n, m, K, int(f64), int(entry == "mbk"), int(inertia), int(aligned), int(gathered),
+                                                ctypes.byref(kernel), ctypes.byref(ns), ctypes.byref(span)))
+    return KERNEL_NAMES[kernel.value], ns.value, span.value
+
+
+SWEEP_N = (1, 64, 127, 128, 129, 4096, 4097, 32640, 32641, 65408, 65409, 65536, 65537, 131072)
+SWEEP_M = (1, 3, 4, 31, 32, 33, 36, 64, 512)
+SWEEP_K = (1, 2, 16, 17, 128, 129, 257, 300, 513, 1000, 2048, 2049, 8321)
+
+
+def test_library_plan_equals_the_restated_dispatch(monkeypatch):
+    """msm_kmeans_label_plan against launch_plan over the full product of the seam values: every threshold of the
+    dispatch from both sides, both row types, both entries, with and without inertia, aligned or not, and the four
+    settings of MSM_LABEL_XCD the tests use."""
+    monkeypatch.delenv("MSM_MBK_SMALL", raising=False)
+    checked = 0
+    for xcd in (None, "0", "1", "3"):
+        if xcd is None:
+            monkeypatch.delenv("MSM_LABEL_XCD", raising=False)
+        else:
+            monkeypatch.setenv("MSM_LABEL_XCD", xcd)
+        tiles = 4 if xcd is None else int(xcd)
+        for n, m, K, f64, entry, inertia, aligned in itertools.product(SWEEP_N, SWEEP_M, SWEEP_K, (False, True), ("label", "mbk"),
+                                                                        (True, False), (True, False)):
+            want = P.launch_plan(n, m, K, f64=f64, entry=entry, inertia=inertia, xcd_tiles=tiles, aligned=aligned)
+            got = library_plan(n, m, K, f64=f64, entry=entry, inertia=inertia, aligned=aligned)
+            assert got == want, (n, m, K, f64, entry, inertia, aligned, xcd, got, want)
+            checked += 1
+    assert checked == 4 * len(SWEEP_N) * len(SWEEP_M) * len(SWEEP_K) * 16
+
+
+def test_cases_sit_on_their_seams(monkeypatch):
     """The dispatch restated in launch_plan (row blocks and centre tiles of 128; XCD launch from 512 row blocks, m >= 64
     and 5..16 tiles; float64 / handle splits below 256 row blocks; the handle's small-batch kernels) puts every case on the
-    path its module docstring names."""
+    path its module docstring names -- and so does the library's own plan."""
+    monkeypatch.delenv("MSM_LABEL_XCD", raising=False)
+    monkeypatch.delenv("MSM_MBK_SMALL", raising=False)
     for (n, m, K, f64, entry), (kernel, ns) in P.SEAMS.items():
         assert P.launch_plan(n, m, K, f64=f64, entry=entry)[:2] == (kernel, ns), (n, m, K, f64, entry)
+        assert library_plan(n, m, K, f64=f64, entry=entry)[:2] == (kernel, ns), (n, m, K, f64, entry)
     listed = {k[:4] + (k[4],) for k in P.SEAMS}
     for n, m, K in P.F32_SCALAR + P.F32_V4 + P.F32_XCD:
         assert (n, m, K, False, "label") in listed
