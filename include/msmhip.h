@@ -483,6 +483,30 @@ int msm_mbk_reassign(msm_mbk_t* h, const void* X, msm_idx_t n, const msm_idx_t* 
                      msm_idx_t n_reassign, double new_count, int on_device);
 int msm_mbk_label(msm_mbk_t* h, const void* X, msm_idx_t n, int32_t* labels, double* inertia, int on_device);
 
+/* Full-batch (Lloyd) k-means, scikit-learn 1.7's _kmeans_single_lloyd on device-resident centres (float32 handle or
+ * float64 handle, as msm_mbk_t).  msm_lloyd_run queues up to max_iter iterations on the n x F rows X (host or device per
+ * on_device) and waits once: label (the msm_mbk_label path), then the centre update -- a stable counting sort of the row
+ * numbers by label and a segmented float64 sum in a fixed order, centre = sum / count rounded once to the rows' type, so
+ * that two runs give the same bits -- then the stop rules on the device: labels equal to the previous iteration's
+ * (*status = MSM_LLOYD_STRICT), else sum ||c_new - c_old||^2 <= tol_abs in float64 (MSM_LLOYD_TOL), else max_iter reached
+ * (MSM_LLOYD_MAXITER).  An iteration that leaves clusters empty stops the queue; the rows farthest from their own centre
+ * (lowest row first among equals) are moved into the empty clusters on the device (scikit-learn's
+ * _relocate_empty_clusters_dense) and the run goes on.  Unless the end was strict the rows are labelled once more against
+ * the final centres.  Out: labels_out[n] (where X lives), *inertia (float64), *n_iter iterations run.
+ * msm_lloyd_plan (pure, needs no device) reports what the update launches for a shape: out8 = {rows per histogram wave,
+ * histogram waves, members per piece of the segmented sum, upper bound on pieces, feature tiles, features per tile,
+ * 16-byte loads (0 / 1), scratch bytes}; aligned: rows and centres start on 16-byte boundaries. */
+typedef struct msm_lloyd msm_lloyd_t;
+enum { MSM_LLOYD_MAXITER = 0, MSM_LLOYD_STRICT = 1, MSM_LLOYD_TOL = 2 };
+int msm_lloyd_create(msm_lloyd_t** h, msm_idx_t n_clusters, msm_idx_t n_features);
+int msm_lloyd_create_f64(msm_lloyd_t** h, msm_idx_t n_clusters, msm_idx_t n_features);
+int msm_lloyd_destroy(msm_lloyd_t* h);
+int msm_lloyd_set_centers(msm_lloyd_t* h, const void* centers);
+int msm_lloyd_get_centers(msm_lloyd_t* h, void* centers);
+int msm_lloyd_run(msm_lloyd_t* h, const void* X, msm_idx_t n, msm_idx_t max_iter, double tol_abs, int32_t* labels_out,
+                  int on_device, double* inertia, msm_idx_t* n_iter, int* status);
+int msm_lloyd_plan(msm_idx_t n, msm_idx_t m, msm_idx_t K, int f64, int aligned, msm_idx_t* out8);
+
 /* ------------------------------------------------------------------------------------------
  * Pre-tICA column scan and scaling.  Replaces the fit / transform arithmetic of
  * msmbuilder.preprocessing.{StandardScaler, MinMaxScaler, MaxAbsScaler}

@@ -176,6 +176,13 @@ def _declare(lib):
     f("msm_mbk_apply_packed", C.c_int, _p, _p, _p, C.c_int)
     f("msm_mbk_reassign", C.c_int, _p, _p, _i64, _p, _p, _i64, C.c_double, C.c_int)
     f("msm_mbk_label", C.c_int, _p, _p, _i64, _p, _f64p, C.c_int)
+    f("msm_lloyd_create", C.c_int, C.POINTER(_p), _i64, _i64)
+    f("msm_lloyd_create_f64", C.c_int, C.POINTER(_p), _i64, _i64)
+    f("msm_lloyd_destroy", C.c_int, _p)
+    f("msm_lloyd_set_centers", C.c_int, _p, _p)
+    f("msm_lloyd_get_centers", C.c_int, _p, _p)
+    f("msm_lloyd_run", C.c_int, _p, _p, _i64, _i64, C.c_double, _p, C.c_int, _f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int))
+    f("msm_lloyd_plan", C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _p)
 
 
 def lib():

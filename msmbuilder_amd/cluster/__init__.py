@@ -1,6 +1,7 @@
 """Clusterers of the MSMBuilder hot path on MI355X (reference: msmbuilder/cluster/__init__.py)."""
 from .base import MultiSequenceClusterMixin
 from .kcenters import KCenters
+from .kmeans import KMeans
 from .minibatchkmeans import MiniBatchKMeans
 
-__all__ = ['KCenters', 'MiniBatchKMeans', 'MultiSequenceClusterMixin']
+__all__ = ['KCenters', 'KMeans', 'MiniBatchKMeans', 'MultiSequenceClusterMixin']

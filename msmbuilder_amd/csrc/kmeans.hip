@@ -1,7 +1,8 @@
 // kmeans.hip -- host side of k-means labelling (GEMM form on MFMA) and the MiniBatchKMeans step for gfx950: the launch
 // plan, the stateless and the handle drivers and the C entry points.  The kernels are in kmeans_label_dev.h (float32
 // tiles), kmeans_f64_dev.h (float64 tiles), kmeans_small_dev.h (small-batch step) and kmeans_update_dev.h (inertia,
-// centre update, convergence, the small helpers); this file is their one translation unit.
+// centre update, convergence, the small helpers) and kmeans_lloyd_dev.h (the full-batch centre update of KMeans); this file
+// is their one translation unit.
 //
 // msmbuilder.cluster.MiniBatchKMeans is a 3-line subclass of scikit-learn's (msmbuilder/cluster/__init__.py:67-69); the
 // arithmetic restated here is scikit-learn's (third-party, unpinned by the reference -- DESIGN.md):
@@ -17,6 +18,7 @@
 #include "kmeans_f64_dev.h"
 #include "kmeans_update_dev.h"
 #include "kmeans_small_dev.h"
+#include "kmeans_lloyd_dev.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -749,6 +751,246 @@ int mbk_create(msm_mbk_t** out, msm_idx_t K, msm_idx_t m, int f64)
 
 }  // namespace
 
+// ---- KMeans: full-batch Lloyd iterations queued on the device ----
+// The centres, their norms and the labelling scratch are those of an msm_mbk handle (labelling goes through mbk_run_label,
+// exactly as msm_mbk_label does); the update's scratch is owned here, sized at the first run and reused.
+struct msm_lloyd {
+    msm_mbk* mbk = nullptr;
+    DevBuf lab[2], order, hist, tabs, pk, partial, shiftsq, st, dist, far, reloc;
+};
+
+namespace msm {
+
+// What the update of one iteration launches.  Pure: no HIP call.
+struct LloydPlan {
+    long long hist_span, groups, piece, pieces_max, ftiles, tile_features, vec, scratch_bytes;
+    long long units;
+    int tu;
+};
+
+static LloydPlan lloyd_plan(long long n, long long m, long long K, bool f64, bool aligned16)
+{
+    LloydPlan pl;
+    const long long esz = f64 ? 8 : 4;
+    pl.hist_span = LH_SPAN;
+    pl.groups = ceil_div(n, LH_SPAN);
+    pl.piece = LL_PIECE;
+    pl.pieces_max = ceil_div(n, LL_PIECE) + K;
+    pl.vec = (aligned16 && (m * esz) % 16 == 0) ? 1 : 0;
+    const long long E = pl.vec ? 16 / esz : 1;
+    pl.units = m / E;
+    int tu = 1;
+    while (tu < LL_TU && tu < pl.units) tu <<= 1;
+    pl.tu = tu;
+    pl.ftiles = ceil_div(pl.units, tu);
+    pl.tile_features = tu * E;
+    pl.scratch_bytes = 2 * n * 4 + n * 4 + K * pl.groups * 4 + (2 * (K + 1) * 8 + (K + 1) * 4) + pl.pieces_max * 4 +
+                       pl.pieces_max * m * 8 + (K + 1) * 8 + LS_COUNT * 4;
+    return pl;
+}
+
+}  // namespace msm
+
+namespace {
+
+template <typename T>
+struct LloydRun {
+    msm_lloyd* h;
+    const T* X;
+    long long n;
+    LloydPlan pl;
+    LloydArgs<T> A;
+    long long* count;
+    long long* start;
+    int* pstart;
+    int* st;
+};
+
+template <typename T>
+int lloyd_reserve(LloydRun<T>& R, double tol_abs)
+{
+    msm_lloyd* h = R.h;
+    msm_mbk* b = h->mbk;
+    const long long K = b->K, m = b->m, n = R.n;
+    int rc;
+    for (int q = 0; q < 2; ++q)
+        if ((rc = h->lab[q].reserve((size_t)n * sizeof(int32_t)))) return rc;
+    if ((rc = h->order.reserve((size_t)n * sizeof(unsigned)))) return rc;
+    if ((rc = h->hist.reserve((size_t)K * R.pl.groups * sizeof(unsigned)))) return rc;
+    if ((rc = h->tabs.reserve((size_t)(2 * (K + 1)) * sizeof(long long) + (size_t)(K + 1) * sizeof(int)))) return rc;
+    if ((rc = h->pk.reserve((size_t)R.pl.pieces_max * sizeof(int)))) return rc;
+    if ((rc = h->partial.reserve((size_t)R.pl.pieces_max * m * sizeof(double)))) return rc;
+    if ((rc = h->shiftsq.reserve((size_t)(K + 1) * sizeof(double)))) return rc;
+    if ((rc = h->st.reserve(LS_COUNT * sizeof(int)))) return rc;
+    R.count = h->tabs.as<long long>();
+    R.start = R.count + (K + 1);
+    R.pstart = reinterpret_cast<int*>(R.start + (K + 1));
+    R.st = h->st.as<int>();
+    LloydArgs<T>& A = R.A;
+    memset(&A, 0, sizeof(A));
+    A.X = R.X;
+    A.n = n;
+    A.m = m;
+    A.K = K;
+    A.C = b->cen<T>();
+    A.cnorm = b->nrm<T>();
+    A.order = h->order.as<unsigned>();
+    A.count = R.count;
+    A.start = R.start;
+    A.pstart = R.pstart;
+    A.pk = h->pk.as<int>();
+    A.partial = h->partial.as<double>();
+    A.shiftsq = h->shiftsq.as<double>();
+    A.shift_out = A.shiftsq + K;
+    A.st = R.st;
+    A.tol = tol_abs;
+    A.units = R.pl.units;
+    A.tu = R.pl.tu;
+    return MSM_OK;
+}
+
+// piece map -> sorted row numbers -> piece sums -> centres, norms, stop rules: everything behind lloyd_base_kernel, which a
+// run that stopped for empty clusters has skipped and the relocation therefore queues again
+template <typename T>
+int lloyd_queue_sums(LloydRun<T>& R, const int32_t* cur)
+{
+    const LloydPlan& pl = R.pl;
+    hipLaunchKernelGGL(lloyd_piecemap_kernel, dim3((unsigned)ceil_div(pl.pieces_max, KNT)), dim3(KNT), 0, stream(), R.pstart, R.A.K,
+                       static_cast<int*>(R.h->pk.p), R.st);
+    hipLaunchKernelGGL(lloyd_scatter_kernel, dim3((unsigned)pl.groups), dim3(64), 0, stream(), cur, R.n, R.A.K, pl.groups,
+                       static_cast<const unsigned*>(R.h->hist.p), R.start, static_cast<unsigned*>(R.h->order.p), R.st);
+    const dim3 grid((unsigned)pl.pieces_max, (unsigned)pl.ftiles);
+    if (pl.vec) hipLaunchKernelGGL((lloyd_segsum_kernel<T, true>), grid, dim3(KNT), 0, stream(), R.A);
+    else hipLaunchKernelGGL((lloyd_segsum_kernel<T, false>), grid, dim3(KNT), 0, stream(), R.A);
+    hipLaunchKernelGGL(lloyd_finish_kernel<T>, dim3((unsigned)R.A.K), dim3(KNT), 0, stream(), R.A);
+    MSM_HIP_CHECK(hipGetLastError());
+    return MSM_OK;
+}
+
+template <typename T>
+int lloyd_queue_iter(LloydRun<T>& R, long long it)
+{
+    msm_lloyd* h = R.h;
+    int32_t* cur = h->lab[it & 1].as<int32_t>();
+    const int32_t* prev = h->lab[(it + 1) & 1].as<int32_t>();
+    KmArgsT<T> P = mbk_args<T>(h->mbk, R.X, nullptr, R.n, R.st + LS_STOP);
+    P.labels = cur;
+    int nb = 0, rc;
+    if ((rc = mbk_run_label<T>(h->mbk, P, false, &nb))) return rc;
+    const LloydPlan& pl = R.pl;
+    hipLaunchKernelGGL(lloyd_hist_kernel, dim3((unsigned)pl.groups), dim3(64), 0, stream(), cur, prev, R.n, R.A.K, pl.groups,
+                       h->hist.as<unsigned>(), R.st);
+    hipLaunchKernelGGL(lloyd_scan_kernel, dim3((unsigned)R.A.K), dim3(KNT), 0, stream(), h->hist.as<unsigned>(), pl.groups, R.count, R.st);
+    hipLaunchKernelGGL(lloyd_base_kernel, dim3(1), dim3(KNT), 0, stream(), R.count, R.A.K, R.start, R.pstart, R.st);
+    MSM_HIP_CHECK(hipGetLastError());
+    return lloyd_queue_sums<T>(R, cur);
+}
+
+// scikit-learn's _relocate_empty_clusters_dense for the iteration that stopped with LLOYD_EMPTY: the n_empty rows farthest
+// from their own (old) centre, lowest row first among equals, leave their clusters and become the empty clusters, in
+// ascending cluster order; then the iteration is finished.  X stays on the device; the K cluster sizes come to the host.
+template <typename T>
+int lloyd_relocate(LloydRun<T>& R, long long it)
+{
+    msm_lloyd* h = R.h;
+    const long long K = R.A.K, n = R.n;
+    std::vector<long long> cnt((size_t)K);
+    MSM_HIP_CHECK(hipMemcpyAsync(cnt.data(), R.count, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, stream()));
+    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    std::vector<int> target;
+    for (long long k = 0; k < K; ++k)
+        if (cnt[(size_t)k] == 0) target.push_back((int)k);
+    const int ne = (int)target.size();
+    if (ne == 0) return fail(MSM_ERR_STATE, "msm_lloyd_run: a relocation without an empty cluster");
+    const int NB = 256;
+    int rc;
+    if ((rc = h->dist.reserve((size_t)n * sizeof(double)))) return rc;
+    if ((rc = h->far.reserve((size_t)NB * (sizeof(double) + sizeof(long long))))) return rc;
+    if ((rc = h->reloc.reserve((size_t)ne * (sizeof(long long) + 2 * sizeof(int))))) return rc;
+    long long* d_row = h->reloc.as<long long>();
+    int* d_donor = reinterpret_cast<int*>(d_row + ne);
+    int* d_target = d_donor + ne;
+    MSM_HIP_CHECK(hipMemcpyAsync(d_target, target.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(R.st + LS_STOP, 0, sizeof(int), stream()));
+    MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `target` is a local vector
+    const int32_t* cur = h->lab[it & 1].as<int32_t>();
+    double* bv = h->far.as<double>();
+    long long* bi = reinterpret_cast<long long*>(bv + NB);
+    hipLaunchKernelGGL(lloyd_dist_kernel<T>, dim3((unsigned)ceil_div(n, 4)), dim3(KNT), 0, stream(), R.X, n, R.A.m, R.A.C, cur,
+                       h->dist.as<double>());
+    for (int q = 0; q < ne; ++q) {
+        hipLaunchKernelGGL(lloyd_far_kernel, dim3(NB), dim3(KNT), 0, stream(), h->dist.as<double>(), n, bv, bi);
+        hipLaunchKernelGGL(lloyd_take_kernel, dim3(1), dim3(KNT), 0, stream(), bv, bi, NB, n, h->dist.as<double>(), cur, q, d_row, d_donor);
+    }
+    MSM_HIP_CHECK(hipGetLastError());
+    R.A.n_reloc = ne;
+    R.A.reloc_row = d_row;
+    R.A.reloc_donor = d_donor;
+    R.A.reloc_target = d_target;
+    rc = lloyd_queue_sums<T>(R, cur);
+    R.A.n_reloc = 0;
+    return rc;
+}
+
+template <typename T>
+int lloyd_run_t(msm_lloyd* h, const T* X, msm_idx_t n, msm_idx_t max_iter, double tol_abs, int32_t* labels_out, int on_device,
+                double* inertia, msm_idx_t* n_iter, int* status)
+{
+    msm_mbk* b = h->mbk;
+    int rc;
+    const T* Xd = X;
+    int32_t* lab_d = labels_out;
+    DevBuf &dX = pool(PS_X), &dL = pool(PS_LAB);
+    if (!on_device) {
+        if ((rc = dX.reserve((size_t)n * b->m * sizeof(T)))) return rc;
+        if ((rc = dL.reserve((size_t)n * sizeof(int32_t)))) return rc;
+        if ((rc = h2d_bulk(dX.p, X, (size_t)n * b->m * sizeof(T)))) return rc;
+        Xd = dX.as<T>();
+        lab_d = dL.as<int32_t>();
+    }
+    LloydRun<T> R;
+    R.h = h;
+    R.X = Xd;
+    R.n = n;
+    R.pl = lloyd_plan(n, b->m, b->K, sizeof(T) == 8, ((((uintptr_t)Xd) | ((uintptr_t)b->centers)) & 15) == 0);
+    if ((rc = lloyd_reserve<T>(R, tol_abs))) return rc;
+    if ((rc = b->part.reserve(1024 * sizeof(double)))) return rc;
+    MSM_HIP_CHECK(hipMemsetAsync(R.st, 0, LS_COUNT * sizeof(int), stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(h->lab[1].p, 0xff, (size_t)n * sizeof(int32_t), stream()));   // "previous" labels of iteration 0: -1
+    int hst[LS_COUNT];
+    long long it = 0;
+    for (int guard = 0;; ++guard) {
+        for (long long i = it; i < max_iter; ++i)
+            if ((rc = lloyd_queue_iter<T>(R, i))) return rc;
+        MSM_HIP_CHECK(hipMemcpyAsync(hst, R.st, sizeof(hst), hipMemcpyDeviceToHost, stream()));
+        MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+        if (hst[LS_STOP] != LLOYD_EMPTY) break;
+        if (guard > max_iter) return fail(MSM_ERR_STATE, "msm_lloyd_run: relocation does not advance");
+        if ((rc = lloyd_relocate<T>(R, hst[LS_ITERS]))) return rc;
+        it = (long long)hst[LS_ITERS] + 1;
+    }
+    const long long done = hst[LS_ITERS];
+    *n_iter = done;
+    *status = hst[LS_STOP];
+    // the labels that are returned and the inertia: strict convergence keeps the last iteration's labels, every other end
+    // labels once more against the final centres
+    KmArgsT<T> P = mbk_args<T>(b, Xd, nullptr, n, nullptr);
+    P.labels = lab_d;
+    int nb = 0;
+    if (hst[LS_STOP] == LLOYD_STRICT) {
+        MSM_HIP_CHECK(hipMemcpyAsync(lab_d, h->lab[(done - 1) & 1].p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, stream()));
+        nb = (int)std::min<long long>(ceil_div(n, 4), 1024);
+        hipLaunchKernelGGL(kmeans_inertia_kernel<T>, dim3(nb), dim3(KNT), 0, stream(), P, b->part.as<double>(), 1);
+        MSM_HIP_CHECK(hipGetLastError());
+    } else if ((rc = mbk_run_label<T>(b, P, true, &nb))) {
+        return rc;
+    }
+    if (!on_device) MSM_HIP_CHECK(hipMemcpyAsync(labels_out, lab_d, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
+    return km_sum_partials(b->part.as<double>(), nb, inertia);
+}
+
+}  // namespace
+
 // dispatch on the handle's element type
 #define MBK_TYPED(h, CALL_F32, CALL_F64) ((h)->f64 ? (CALL_F64) : (CALL_F32))
 
@@ -965,6 +1207,67 @@ int msm_mbk_step_f64(const double* X, msm_idx_t n, msm_idx_t m, const msm_idx_t*
                      int apply_update, int on_device)
 {
     return mbk_step_stateless_t<double>(X, n, m, batch_idx, B, centers, counts, K, batch_inertia, batch_sums, batch_counts, apply_update, on_device);
+}
+
+/* ---- KMeans (full-batch Lloyd): see include/msmhip.h ---- */
+static int lloyd_create(msm_lloyd_t** out, msm_idx_t K, msm_idx_t m, int f64)
+{
+    if (!out) return fail(MSM_ERR_INVALID, "msm_lloyd_create: bad argument");
+    msm_mbk* b = nullptr;
+    const int rc = mbk_create(&b, K, m, f64);
+    if (rc) return rc;
+    msm_lloyd* h = new msm_lloyd();
+    h->mbk = b;
+    *out = h;
+    return MSM_OK;
+}
+
+int msm_lloyd_create(msm_lloyd_t** out, msm_idx_t K, msm_idx_t m) { return lloyd_create(out, K, m, 0); }
+int msm_lloyd_create_f64(msm_lloyd_t** out, msm_idx_t K, msm_idx_t m) { return lloyd_create(out, K, m, 1); }
+
+int msm_lloyd_destroy(msm_lloyd_t* h)
+{
+    if (!h) return MSM_OK;
+    (void)msm_mbk_destroy(h->mbk);   // (synchronises the stream first)
+    delete h;
+    return MSM_OK;
+}
+
+int msm_lloyd_set_centers(msm_lloyd_t* h, const void* centers)
+{
+    if (!h || !centers) return fail(MSM_ERR_STATE, "msm_lloyd_set_centers: null argument");
+    const std::vector<double> zero((size_t)h->mbk->K, 0.0);   // (all-zero bits: K zero counts of either type)
+    return msm_mbk_set(h->mbk, centers, zero.data());
+}
+
+int msm_lloyd_get_centers(msm_lloyd_t* h, void* centers)
+{
+    if (!h || !centers) return fail(MSM_ERR_STATE, "msm_lloyd_get_centers: null argument");
+    return msm_mbk_get(h->mbk, centers, nullptr);
+}
+
+int msm_lloyd_run(msm_lloyd_t* h, const void* X, msm_idx_t n, msm_idx_t max_iter, double tol_abs, int32_t* labels_out,
+                  int on_device, double* inertia, msm_idx_t* n_iter, int* status)
+{
+    if (!h || !X || !labels_out || !inertia || !n_iter || !status) return fail(MSM_ERR_STATE, "msm_lloyd_run: null argument");
+    if (n < 1 || n >= 0x7fffffffLL || max_iter < 1) return fail(MSM_ERR_INVALID, "msm_lloyd_run: bad shape");
+    return MBK_TYPED(h->mbk, lloyd_run_t<float>(h, (const float*)X, n, max_iter, tol_abs, labels_out, on_device, inertia, n_iter, status),
+                     lloyd_run_t<double>(h, (const double*)X, n, max_iter, tol_abs, labels_out, on_device, inertia, n_iter, status));
+}
+
+int msm_lloyd_plan(msm_idx_t n, msm_idx_t m, msm_idx_t K, int f64, int aligned, msm_idx_t* out8)
+{
+    if (n < 1 || m < 1 || K < 1 || !out8) return fail(MSM_ERR_INVALID, "msm_lloyd_plan: bad argument");
+    const LloydPlan pl = lloyd_plan(n, m, K, f64 != 0, aligned != 0);
+    out8[0] = pl.hist_span;
+    out8[1] = pl.groups;
+    out8[2] = pl.piece;
+    out8[3] = pl.pieces_max;
+    out8[4] = pl.ftiles;
+    out8[5] = pl.tile_features;
+    out8[6] = pl.vec;
+    out8[7] = pl.scratch_bytes;
+    return MSM_OK;
 }
 
 }  // extern "C"
