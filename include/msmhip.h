@@ -26,6 +26,7 @@
  *   msm_assign_nearest_*  libdistance/src/assign.hpp:6-91 (via libdistance.pyx:82-131)
  *   msm_pdist_* / msm_sumdist_*  libdistance/src/pdist.hpp:4-88, sumdist.hpp:4-44 (via libdistance.pyx:182-226, 273-310)
  *   msm_kcenters_fit_*    cluster/kcenters.py:79-102 (_KCenters.fit's k-pass loop)
+ *   msm_regspatial_fit_*  cluster/regularspatial.py:69-81 (_RegularSpatial.fit's per-row loop)
  *   msm_kmeans_* / msm_mbk_*  sklearn MiniBatchKMeans arithmetic behind
  *                     cluster/__init__.py:67-69 (third-party)
  * The exact reference signatures of libdistance are additionally exported,
@@ -380,6 +381,29 @@ int msm_kcenters_last_wide_stats(msm_idx_t* out2);
 /* Batched screened passes of the last k-centers fit (several centres per pass): out1 = {rounds whose threshold list was
  * unusable, so that the pass applied one centre}; 0 when the fit ran no batches. */
 int msm_kcenters_last_batch_fallbacks(msm_idx_t* out1);
+
+/* Regular spatial (leader) clustering (cluster/regularspatial.py:69-81): row 0 is a centre, row i > 0 is a centre iff
+ * metric(X[c], X[i]) > d_min for EVERY centre c chosen before it (a NaN distance or d == d_min makes none; d_min < 0
+ * makes every row with finite distances one).  Runs in row blocks on the device -- screen against the known centres,
+ * compact the uncovered rows, resolve them in row order in one workgroup -- with one host synchronisation per block;
+ * every distance is the exact one of msm_dist_*, so ids equal the sequential loop's.  X (n x m) follows on_device.
+ *   block_rows: 0 = the library's rule (4,096 rows first; x 4 after a block that found at most one centre per 64 rows,
+ *   / 2 after one that found more than one per 8, within [1,024, 2^22]); > 0 = every block has this many rows (tests put
+ *   block seams inside small inputs with it; at most 2^22).
+ *   *n_centers (host) = K, which no one knows in advance: the centre list is owned by the library, grows by doubling
+ *   (no cap on K), and stays valid until the next fit.  msm_regspatial_result_* then copies it out: ids (host, K) = the
+ *   chosen rows in the order chosen (ascending), centers (host, K x m, X's element type) = X[ids].  MSM_ERR_STATE
+ *   when the last finished fit was not of this element type.
+ * On an error (MSM_ERR_METRIC for a null / unknown metric name, MSM_ERR_INVALID for a bad shape) nothing is written. */
+int msm_regspatial_fit_f32(const float* X, msm_idx_t n, msm_idx_t m, const char* metric, double d_min,
+                           msm_idx_t block_rows, int on_device, msm_idx_t* n_centers);
+int msm_regspatial_fit_f64(const double* X, msm_idx_t n, msm_idx_t m, const char* metric, double d_min,
+                           msm_idx_t block_rows, int on_device, msm_idx_t* n_centers);
+int msm_regspatial_result_f32(msm_idx_t* ids, float* centers);
+int msm_regspatial_result_f64(msm_idx_t* ids, double* centers);
+/* What the last regular spatial fit of this process did: out4 = {blocks run, survivors handed to the resolve step,
+ * resolve rounds (= centres chosen), growths of the centre list}. */
+int msm_regspatial_last_stats(msm_idx_t* out4);
 
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works

@@ -3,5 +3,6 @@ from .base import MultiSequenceClusterMixin
 from .kcenters import KCenters
 from .kmeans import KMeans
 from .minibatchkmeans import MiniBatchKMeans
+from .regularspatial import RegularSpatial
 
-__all__ = ['KCenters', 'KMeans', 'MiniBatchKMeans', 'MultiSequenceClusterMixin']
+__all__ = ['KCenters', 'KMeans', 'MiniBatchKMeans', 'RegularSpatial', 'MultiSequenceClusterMixin']
