@@ -193,7 +193,10 @@ template <typename T>
 static int km_run_label(KmArgsT<T> P, const KmPlan& pl, DevBuf& pv, DevBuf& pi, double* partial, const SmallArgs* small = nullptr)
 {
     int rc;
-    const bool cand = pl.nsplit > 1 || pl.kernel == MSM_KM_LABEL64;   // (the 64 x 64 kernel writes candidates whatever their number)
+    // One split: the kernel writes the labels itself (jspan = 0).  The 64 x 64 kernel used to be handed a span here
+    // whatever the number of its splits; with one split (K <= 64) it then wrote a candidate that kmeans_inertia_kernel
+    // (which merges only when nsplit > 1) never read, and the step ran on whatever the label buffer held.
+    const bool cand = pl.nsplit > 1;
     if (cand && pl.kernel != MSM_KM_SMALL) {
         if ((rc = pv.reserve((size_t)pl.nsplit * P.n * sizeof(T)))) return rc;
         if ((rc = pi.reserve((size_t)pl.nsplit * P.n * sizeof(int)))) return rc;

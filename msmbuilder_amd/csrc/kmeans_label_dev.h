@@ -263,7 +263,10 @@ __device__ __forceinline__ void km64_load(Km64Stage& st, const KmArgs& P, const 
     }
 }
 
-// `inb`: this thread's four columns of the step lie inside the row (else the stage holds clamped-address data: zeros go to LDS)
+// `inb`: the first of this thread's four columns of the step lies inside the row (else the stage holds clamped-address data:
+// zeros go to LDS).  16-byte path: m % 4 == 0, so the four are inside or outside together.  Other widths: km64_load has
+// zeroed the columns past the row one by one, and the last, partial group of four must go to LDS as it is -- asking for
+// all four columns to be inside dropped the last m % 4 features from every dot product.
 __device__ __forceinline__ void km64_store(const Km64Stage& st, float* Xs, float* Cs, int tid, bool inb)
 {
     constexpr int CPR = KB64 / 4, RPP = KNT / CPR;
@@ -320,7 +323,7 @@ __global__ __launch_bounds__(KNT) void kmeans_label64_kernel(KmArgs P)
         for (int q = 0; q < 4; ++q)
             if (q < nk) km64_load(st[q], P, xrow, j0, q * KB64, tid);
         __syncthreads();  // the previous centre tile's last fragment reads are done
-        km64_store(st[0], Xs, Cs, tid, c4s + 3 < P.m);
+        km64_store(st[0], Xs, Cs, tid, c4s < P.m);
         __syncthreads();
         for (int s0 = 0; s0 < nk; s0 += 4) {
 #pragma unroll
@@ -343,7 +346,7 @@ __global__ __launch_bounds__(KNT) void kmeans_label64_kernel(KmArgs P)
                     }
                     if (s + 1 < nk)
                         km64_store(st[(q + 1) & 3], Xs + (buf ^ 1) * (KS64 * KP64), Cs + (buf ^ 1) * (KS64 * KP64), tid,
-                                   (s + 1) * KB64 + c4s + 3 < P.m);
+                                   (s + 1) * KB64 + c4s < P.m);
                     __syncthreads();
                 }
             }

@@ -114,7 +114,9 @@ __global__ __launch_bounds__(KNT) void kmeans_inertia_kernel(KmArgsT<T> P, doubl
 // msm_mbk_run: end of one queued step.  Sums the inertia partials, then plays sklearn's _mini_batch_convergence
 // (_kmeans.py:1963-2027, tol = 0 and verbose = 0 branch) in float64 on the device so that the host does not have to
 // look at every step: st = {ewa, ewa_min, no_improvement, have_ewa, have_min, steps_done}.  Plain IEEE operations in
-// the host's order (no contraction: __dmul_rn / __dadd_rn).  Executed by the LAST workgroup of mbk_update_kernel to
+// the host's order: contraction is switched off for the function by pragma (HIP's __dmul_rn / __dadd_rn are plain `*` and
+// `+` once inlined, and the compiler fused ewa * (1 - alpha) + bi * alpha into one fma: an ulp or two off scikit-learn's
+// moving average, enough to decide `ewa < ewa_min` the other way on a tie).  Executed by the LAST workgroup of mbk_update_kernel to
 // finish (an arrival counter), not by a launch of its own: between dependent launches the GPU idles for ~10-15 us,
 // which at 85 us of work per step is what a launch costs.
 struct MbkConv {
@@ -131,6 +133,7 @@ struct MbkConv {
 
 __device__ __forceinline__ void mbk_converge(const MbkConv& cv, double* red)
 {
+#pragma clang fp contract(off)
     double s = 0.0;
     for (int i = threadIdx.x; i < cv.nb; i += KNT) s += cv.partial[i];
     red[threadIdx.x] = s;
@@ -151,7 +154,7 @@ __device__ __forceinline__ void mbk_converge(const MbkConv& cv, double* red)
         ewa = bi;
         st[3] = 1.0;
     } else {
-        ewa = __dadd_rn(__dmul_rn(st[0], __dadd_rn(1.0, -cv.alpha)), __dmul_rn(bi, cv.alpha));
+        ewa = st[0] * (1.0 - cv.alpha) + bi * cv.alpha;
     }
     st[0] = ewa;
     if (st[4] == 0.0 || ewa < st[1]) {

@@ -33,7 +33,9 @@ test_kmeans_label_rule.py pins this table against both and holds km_plan, throug
   * both merge routes: msm_kmeans_label_* with a null inertia pointer merges in kmeans_label_reduce_kernel, with one in
     kmeans_inertia_kernel: identical labels required on the split shapes.
   * msm_mbk_label: (4096,64,300) kmeans_label64_kernel in 5 splits of 64, (4097,64,300) the general kernel in 3 splits,
-    (65536,32,100) mbk_small_label_kernel, (65537,32,100) the general kernel; (100,4,8321) float64.
+    (65536,32,100) mbk_small_label_kernel, (65537,32,100) the general kernel; (100,4,8321) float64; (300,33,100) and
+    (200,67,60) kmeans_label64_kernel at widths that are no multiple of 4 (the last, partial group of four features of
+    a row), the second in ONE split (K <= 64): the kernel writes the labels itself, nothing is merged.
   * offset data (everything + 3): (257,36,129), (65409,64,513).
   * NaN rows (labels only): an all-NaN row and a row with one NaN, each at the first row of a block and at row n - 1.
   * integer lattices: every float32 operation of the GEMM form is exact, exact ties between DIFFERENT centres are common
@@ -219,7 +221,7 @@ F32_V4 = [(300, 4, 130), (257, 36, 129), (1000, 512, 1000), (128, 64, 128), (129
 F32_XCD = [(65408, 64, 513), (65409, 64, 512), (65409, 64, 513), (65537, 64, 513), (65537, 64, 2048), (65537, 64, 2049)]
 INERTIA = [(n, m, 10) for m in (6, 8) for n in (1, 2, 7, 8, 9, 16384, 16385, 16391)]
 F64 = [(32640, 4, 257), (32641, 4, 257), (100, 4, 129), (100, 4, 8321), (300, 17, 300)]
-MBK_F32 = [(4096, 64, 300), (4097, 64, 300), (65536, 32, 100), (65537, 32, 100)]
+MBK_F32 = [(4096, 64, 300), (4097, 64, 300), (65536, 32, 100), (65537, 32, 100), (300, 33, 100), (200, 67, 60)]
 MBK_F64 = [(100, 4, 8321)]
 OFFSET = [(257, 36, 129), (65409, 64, 513)]
 NAN = [(65409, 64, 513, False), (100, 4, 8321, True), (32640, 4, 257, True)]
@@ -242,6 +244,7 @@ SEAMS = {
     (4096, 64, 300, False, "mbk"): ("label64", 5), (4097, 64, 300, False, "mbk"): ("v4", 3),
     (65536, 32, 100, False, "mbk"): ("small", 1), (65537, 32, 100, False, "mbk"): ("v4", 1),
     (100, 4, 8321, True, "mbk"): ("f64", 66),
+    (300, 33, 100, False, "mbk"): ("label64", 2), (200, 67, 60, False, "mbk"): ("label64", 1),
 }
 
 
