@@ -108,6 +108,8 @@ def cdist(XA, XB, metric):
     ax = Arr(XA, dt)
     ab = _host(XB, dt)
     out = empty_like_placement(ax, (ax.shape[0], ab.shape[0]), np.float64)
+    if ax.shape[0] == 0 or ab.shape[0] == 0:
+        return out   # no pair (cdist.hpp's loops do not run; an empty device tensor has no address)
     aout = Arr(out, np.float64)
     fn = getattr(_lib.lib(), "msm_cdist_" + kind)
     check(fn(ax.vp, C.c_void_p(ab.ctypes.data), m, ax.shape[0], ab.shape[0], ax.shape[1], aout.vp,
@@ -135,6 +137,8 @@ def dist(X, y, metric, X_indices=None):
             raise ValueError("X and X_indices must live on the same side (host or device)")
         n = idx.shape[0]
     out = empty_like_placement(ax, (n,), np.float64)
+    if n == 0:
+        return out   # no row (an empty device tensor has no address, and a null X_indices would mean "every row")
     aout = Arr(out, np.float64)
     fn = getattr(_lib.lib(), "msm_dist_" + kind)
     check(fn(ax.vp, C.c_void_p(ay.ctypes.data), m, ax.shape[0], ax.shape[1],
@@ -165,6 +169,8 @@ def pdist(X, metric, X_indices=None):
             raise ValueError("X and X_indices must live on the same side (host or device)")
         n = idx.shape[0]
     out = empty_like_placement(ax, (n * (n - 1) // 2,), np.float64)
+    if n < 2:
+        return out   # no pair (an empty device tensor has no address)
     aout = Arr(out, np.float64)
     fn = getattr(_lib.lib(), "msm_pdist_" + kind)
     check(fn(ax.vp, m, ax.shape[0], ax.shape[1], idx.vp if idx is not None else None, n, aout.vp, ax.on_device))

@@ -74,6 +74,40 @@ def test_libdistance_oracle_vs_compiled_reference(oracle):
                     assert _same(np.float64(oracle.sumdist(X, m, pairs)), np.float64(ref.sumdist(X, m, pairs)))
 
 
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("metric", METRICS)
+def test_libdistance_oracle_vs_compiled_reference_special_rows(oracle, metric, dt):
+    """Zero-laden and non-finite rows (tests/libdistance_cases.py), where the random rows above never go: canberra's
+    `sdenom > 0` guard, 0/0 = NaN in braycurtis and jaccard, hamming on -0.0, NaN / +-inf against assign's strict `<`.
+    The GPU tests hold the kernels to the oracle on these rows, so the oracle is held to the reference on them here."""
+    from libdistance_cases import special_centres, special_rows
+    ref = Ref()
+    X, rows = special_rows(400, 36, dt, seed=5)
+    Y = special_centres(X, rows, 12, seed=5)
+    rs = np.random.RandomState(6)
+    idx = np.concatenate([rows, rs.randint(0, 400, size=36)]).astype(np.int64)
+    pairs = np.concatenate([rs.randint(0, 400, size=(90, 2)), np.stack([rows, rows[::-1]], axis=1),
+                            np.stack([rows, rows], axis=1)]).astype(np.int64)
+    with np.errstate(all="ignore"):
+        c = oracle.cdist(X, Y, metric)
+        assert _same(c, ref.cdist(X, Y, metric))
+        if metric in ("braycurtis", "jaccard"):
+            assert np.isnan(c[rows[0], 1])          # zero row against zero centre: 0/0
+        if metric == "canberra":
+            assert c[rows[0], 1] == 0.0             # every term skipped by the guard
+        for ix in (None, idx):
+            l1, i1 = oracle.assign_nearest(X, Y, metric, ix)
+            l2, i2 = ref.assign_nearest(X, Y, metric, ix)
+            assert np.array_equal(l1, l2) and _same(np.float64(i1), np.float64(i2))
+            assert _same(oracle.dist(X, Y[2], metric, ix), ref.dist(X, Y[2], metric, ix))
+            assert _same(oracle.pdist(X, metric, ix), ref.pdist(X, metric, ix))
+        assert _same(np.float64(oracle.sumdist(X, metric, pairs)), np.float64(ref.sumdist(X, metric, pairs)))
+        # the sequential sum is NaN or inf for most metrics here; the finite pairs on their own
+        fin = pairs[:90][np.isfinite(X[pairs[:90]]).all(axis=(1, 2))]
+        assert _same(np.float64(oracle.sumdist(X, metric, fin)), np.float64(ref.sumdist(X, metric, fin)))
+
+
 def test_libdistance_oracle_error_contract(oracle):
     X, Y = np.zeros((3, 2), np.float32), np.zeros((2, 2), np.float32)
     with pytest.raises(ValueError):
