@@ -1,0 +1,530 @@
+"""The row-sharded k-centers fit, msm_kcenters_fit_sharded_f32/_f64 (csrc/distance.hip kcenters_fit_sharded_impl): what
+every multi-GPU run of KCenters executes and what bench.py times through KCenters._force_sharded in a world of one.
+
+The three loops of the sharded fit and what selects them (FC = 32 float32 / 16 float64 features, the register path):
+
+- batched: float64 rows of at most FC features, euclidean, K > 8, MSM_KC_BATCH not 0 -- whatever the shard's size.  Two
+  plain probe passes, then rounds of several centres (kcb_select_sharded_kernel, kcenters_batch_pass_kernel,
+  kcb_pack_kernel, kcb_boot_records_kernel; kcb_empty_record_kernel on a rank without rows).
+  Stats: st[1] == 2 and 0 < st[2] < K - 2.  Where every distance is 0 or inf no threshold list can form and every round
+  falls back to the one row the per-block partials name: st[2] == K - 2 == msm_kcenters_last_batch_fallbacks
+  ("batched1" below; the constant matrix and the non-finite rows).  Rows around hubs give one centre per round for the
+  first ten centres or so (the listing threshold trails distances that fall fast), so the K = 9 and 10 cases run on
+  kcenters_sharded_cases.batch_rows: the same bulk plus 16 far rows whose levels of nearly equal distance let a round take
+  two centres -- 6 rounds for the 7 centres after the probes at K = 9, 7 for 8 at K = 10 (printed by the test).
+- fused: any other fit of rows of at most FC features.  Select and candidate record inside kcenters_pass_kernel<T, M,
+  true> (sel_cands, cand_out, the arrival counter); norm metrics prune through the 2048-entry Dc table.  Stats: st[1] == K,
+  st[2] == 0.  From KSC_MIN_ROWS = 65,536 rows on, float64 euclidean fits with K > 8 (reached with MSM_KC_BATCH=0) run
+  kcenters_screen_pass_kernel after four plain passes: st[1] == 4, st[2] == K - 4.
+- generic: rows longer than FC (and a rank without rows).  kcenters_pass_dev_impl + kc_candidate_kernel +
+  kc_select_kernel per centre; the grid is cut to wide_grid(n) = min(ceil(n / DT), 2 C) when wide_ok holds (row length a
+  multiple of 16 bytes, base 16-byte aligned).  This loop leaves the stats untouched: every sharded fit below is preceded
+  by a three-row fit, and a generic case asserts that the stats are still that fit's.
+
+Part 1 runs in this process, which has no communicator (msm_comm_info kind 0, asserted before every test): the gathered
+records alias the rank's own record (cands == cand, recsG == recL), the layout bench.py measures.  Part 2 starts two
+ranks on the host-callback transport.
+
+Seams and the sizes chosen for them (DT = 256 rows per tile, KC_MAXBLK = 1024, C = compute units read from torch):
+
+- per-lane vector width of row_vecw, float32: m = 1, 2, 3, 4, 31, 32 -> 4, 8, 4, 16, 4, 16 bytes; m = 4 on rows offset
+  by one element -> 4;
+- tile edges: n = 1, 255, 256, 257; more than one wave of workgroups: 70,001; the grid-stride tile loop (more tiles than
+  KC_MAXBLK workgroups): 271,000 x 4 float32 and KC_MAXBLK DT + 9,000 = 271,144 float64 rows;
+- K = 1, 2, 9, 30 (fused float32); K = 8 / 9 and the metric decide batched against fused for float64;
+- KSC_MIN_ROWS: n = 65,535 (plain) and 65,536 (screened) with MSM_KC_BATCH=0;
+- the np = ceil(m / 2) instantiations of the batched kernels, 1 .. 8, odd and even widths: m = 1, 2, 3, 10, 15, 16;
+- FC: m = 33 float32 / 17 float64 (one past it, never wide_ok), 36 / 18 (wide_ok), 36 float32 at an offset address
+  (wide_ok false), all at n = 3,000; wide_grid: n = 2 C DT - 2,000 and 2 C DT + 5,000 for 36 float32 / 18 float64, K = 24;
+- row_offset = 5,000,000,011 (beyond int32) in a world of one;
+- KC_PRUNE_MAX = 2048: K = 2,100 on 6,000 x 3 rows (nprev capped, labels >= 2048 at the `lab < nprev` guard), in the
+  sharded fit (float32 fused, float64 batched) and in the single fit;
+- ties (the lower of two equal rows wins), a constant matrix, K = n, a NaN row and a +inf row.
+
+References, in this order of authority:
+
+1. Oracle().kcenters_fit of oracle/libdistance_oracle.py: ids, labels and float64 distances bit for bit, for every case
+   of at most 5e8 row x feature x centre terms (here: every case);
+2. the single fit msm_kcenters_fit2_* on the same device rows and seed: ids, labels, distances (equal_nan) and centres bit
+   for bit, every case;
+3. inertia: |inertia - math.fsum(distances)| <= n 2^-53 fsum, the bound of any fp64 summation order of n non-negative
+   terms (each of the n - 1 additions rounds by at most 2^-53 of a partial sum, and no partial sum exceeds the total).
+   With inf or NaN among the distances: the same non-finite value as numpy.sum.
+"""
+import ctypes as C
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from kcenters_sharded_cases import TWO_RANK_CASES, batch_rows, tie_rows
+from test_gpu_kcenters_grid import DT, KC_MAXBLK, KNOBS, ORACLE_TERMS, _free_device_memory, _n, _rows  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_F32, _F64 = np.float32, np.float64
+METRICS = ["euclidean", "sqeuclidean", "cityblock", "chebyshev", "canberra", "braycurtis", "hamming", "jaccard"]
+ROW_OFFSET = 5_000_000_011
+SENTINEL_ROWS = 3
+
+
+@pytest.fixture(autouse=True)
+def _no_communicator(gpu):
+    """Part 1 is about the aliased layout of a process without a communicator."""
+    r, w, k = C.c_int(), C.c_int(), C.c_int()
+    gpu.lib().msm_comm_info(C.byref(r), C.byref(w), C.byref(k))
+    assert k.value == 0, (r.value, w.value, k.value)
+    yield
+
+
+def _stats():
+    from msmbuilder_amd import _lib
+    st = (C.c_int64 * 5)()
+    fb = (C.c_int64 * 1)()
+    _lib.check(_lib.lib().msm_kcenters_last_stats(st))
+    _lib.check(_lib.lib().msm_kcenters_last_batch_fallbacks(fb))
+    return list(st), int(fb[0])
+
+
+def _set_knobs(monkeypatch, env):
+    for key in KNOBS:
+        monkeypatch.delenv(key, raising=False)
+    for key, v in (env or {}).items():
+        monkeypatch.setenv(key, v)
+
+
+def _call_sharded(X, k, metric, seed, row_offset):
+    import torch
+    from msmbuilder_amd import _lib
+    from msmbuilder_amd._lib import Arr
+    n, m = X.shape
+    ax = Arr(X)
+    assert ax.ptr == X.data_ptr()
+    kind = "f64" if X.dtype == torch.float64 else "f32"
+    labels = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+    dist = torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
+    ids = np.full(k, -7, dtype=np.int64)
+    centres = np.full((k, m), -7, dtype=ax.dtype)
+    inertia = C.c_double(-7.0)
+    fn = getattr(_lib.lib(), "msm_kcenters_fit_sharded_" + kind)
+    _lib.check(fn(ax.vp, n, m, k, metric.encode(), int(seed), int(row_offset), C.c_void_p(labels.data_ptr()),
+                  C.c_void_p(dist.data_ptr()), ids.ctypes.data, centres.ctypes.data, C.byref(inertia)))
+    return dict(ids=ids.tolist(), labels=labels.cpu().numpy(), dist=dist.cpu().numpy(), centres=centres,
+                inertia=float(inertia.value))
+
+
+def _sharded(monkeypatch, X, k, metric="euclidean", seed=3, row_offset=0, env=None):
+    """The sharded fit of X as the only shard, called as _KCenters._fit_sharded calls it.  A three-row fit comes first: it
+    sets the stats, which the generic loop does not touch."""
+    import torch
+    _set_knobs(monkeypatch, None)
+    _call_sharded(torch.arange(SENTINEL_ROWS, dtype=torch.float32, device="cuda").view(SENTINEL_ROWS, 1), 1, "euclidean", 0, 0)
+    assert _stats()[0][:3] == [SENTINEL_ROWS, 1, 0]
+    _set_knobs(monkeypatch, env)
+    r = _call_sharded(X, k, metric, seed, row_offset)
+    r["st"], r["fb"] = _stats()
+    _set_knobs(monkeypatch, None)
+    return r
+
+
+def _single(monkeypatch, X, k, metric="euclidean", seed=3, env=None):
+    """msm_kcenters_fit2_* on the same device rows."""
+    import torch
+    from msmbuilder_amd import _lib
+    from msmbuilder_amd._lib import Arr
+    n, m = X.shape
+    ax = Arr(X)
+    kind = "f64" if X.dtype == torch.float64 else "f32"
+    labels = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+    dist = torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
+    ids = np.full(k, -7, dtype=np.int64)
+    centres = np.full((k, m), -7, dtype=ax.dtype)
+    inertia = C.c_double(-7.0)
+    _set_knobs(monkeypatch, env)
+    fn = getattr(_lib.lib(), "msm_kcenters_fit2_" + kind)
+    _lib.check(fn(ax.vp, n, m, k, metric.encode(), int(seed), ids.ctypes.data, C.c_void_p(labels.data_ptr()),
+                  C.c_void_p(dist.data_ptr()), C.byref(inertia), 1, centres.ctypes.data))
+    _set_knobs(monkeypatch, None)
+    return dict(ids=ids.tolist(), labels=labels.cpu().numpy(), dist=dist.cpu().numpy(), centres=centres,
+                inertia=float(inertia.value))
+
+
+def _assert_loop(r, loop, n, k):
+    """msm_kcenters_last_stats: st[0] rows, st[1] plain passes, st[2] screened passes (rounds when batched)."""
+    st, fb = r["st"], r["fb"]
+    if loop == "generic":      # untouched: still the three-row fit's
+        assert st[:3] == [SENTINEL_ROWS, 1, 0] and n != SENTINEL_ROWS, st
+        return
+    assert st[0] == n, st
+    if loop == "batched":
+        assert st[1] == 2 and 0 < st[2] < k - 2, (st, fb)
+    elif loop == "batched1":   # one centre per round: every round fell back to the row the partials name
+        assert st[1] == 2 and st[2] == k - 2 and fb == k - 2, (st, fb)
+    elif loop == "plain":
+        assert st[1] == k and st[2] == 0, st
+    elif loop == "screened":
+        assert st[1] == 4 and st[2] == k - 4, st
+    else:
+        raise AssertionError(loop)
+
+
+def _assert_inertia(inertia, dist):
+    n = len(dist)
+    if np.isfinite(dist).all():
+        tot = math.fsum(dist)
+        assert abs(inertia - tot) <= n * 2.0 ** -53 * tot, (inertia, tot)
+    else:
+        tot = float(np.sum(dist))
+        assert (np.isnan(tot) and np.isnan(inertia)) or inertia == tot, (inertia, tot)
+
+
+def _assert_bit_equal(a, b, row_offset=0):
+    """ids (less the offset), labels, distances and centres of two fits."""
+    assert [i - row_offset for i in a["ids"]] == b["ids"], (a["ids"], b["ids"])
+    assert np.array_equal(a["labels"], b["labels"])
+    assert np.array_equal(a["dist"], b["dist"], equal_nan=True)
+    assert a["centres"].dtype == b["centres"].dtype
+    assert np.array_equal(a["centres"], b["centres"], equal_nan=True)
+
+
+_ORACLE = []
+
+
+def _oracle_fit(Xh, k, metric, seed):
+    from oracle.libdistance_oracle import Oracle
+    if not _ORACLE:
+        _ORACLE.append(Oracle())
+    n, m = Xh.shape
+    assert n * m * k <= ORACLE_TERMS
+    ids, labels, dist = _ORACLE[0].kcenters_fit(Xh, k, metric, seed)
+    return dict(ids=[int(i) for i in ids], labels=labels, dist=dist, centres=Xh[ids])
+
+
+def _check(monkeypatch, X, r, loop, k, metric="euclidean", seed=3, env=None, Xh=None, single=None):
+    """One sharded fit against the three references; returns (host rows, single fit) for reuse."""
+    n = X.shape[0]
+    _assert_loop(r, loop, n, k)
+    if Xh is None:
+        Xh = X.cpu().numpy()
+    o = _oracle_fit(Xh, k, metric, seed)
+    assert r["ids"] == o["ids"], (r["ids"], o["ids"])
+    assert np.array_equal(r["labels"], o["labels"])
+    assert np.array_equal(r["dist"], o["dist"])
+    assert np.array_equal(r["centres"], o["centres"], equal_nan=True)
+    if single is None:
+        single = _single(monkeypatch, X, k, metric, seed, env)
+    _assert_bit_equal(r, single)
+    _assert_inertia(r["inertia"], r["dist"])
+    return Xh, single
+
+
+# ---------------------------------------------------------------------------------------------------- fused, float32
+@pytest.mark.parametrize("m,offset", [(1, False), (2, False), (3, False), (4, False), (31, False), (32, False), (4, True)],
+                         ids=["m1", "m2", "m3", "m4", "m31", "m32", "m4-offset"])
+def test_fused_float32_widths_and_tile_edges(gpu, monkeypatch, m, offset):
+    """Every per-lane vector width of the register path at the tile edges and past one wave of workgroups, K = 1, 2, 9, 30."""
+    for n in (1, 255, 256, 257, 70_001):
+        X = _rows(n, m, _F32, seed=m * 11 + n % 97, offset=offset)
+        Xh = X.cpu().numpy()
+        for k in (1, 2, 9, 30):
+            if k > n:
+                continue
+            seed = (n * 5) // 7
+            r = _sharded(monkeypatch, X, k, seed=seed)
+            _check(monkeypatch, X, r, "plain", k, seed=seed, Xh=Xh)
+
+
+@pytest.mark.parametrize("k", [2, 30])
+def test_fused_float32_tile_loop(gpu, monkeypatch, k):
+    """More tiles than KC_MAXBLK workgroups: each workgroup strides over two tiles (and some over one)."""
+    n = 271_000
+    assert n > KC_MAXBLK * DT
+    X = _rows(n, 4, _F32, seed=8)
+    r = _sharded(monkeypatch, X, k, seed=123_456)
+    _check(monkeypatch, X, r, "plain", k, seed=123_456)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_fused_float32_metrics(gpu, monkeypatch, metric):
+    """All eight vector metrics through the fused loop; the norm metrics prune through the Dc table, the others do not."""
+    X = _rows(3_001, 10, _F32, seed=21)
+    r = _sharded(monkeypatch, X, 12, metric)
+    _check(monkeypatch, X, r, "plain", 12, metric)
+
+
+# ---------------------------------------------------------------------------------------------------- fused, float64
+@pytest.mark.parametrize("metric,k", [("euclidean", 8), ("euclidean", 3), ("cityblock", 30), ("chebyshev", 30), ("canberra", 30)])
+def test_fused_float64_not_batched(gpu, monkeypatch, metric, k):
+    """float64 rows of 10 features that the batched loop does not take: K <= 8, or a metric other than euclidean."""
+    X = _rows(5_000, 10, _F64, seed=31)
+    r = _sharded(monkeypatch, X, k, metric)
+    _check(monkeypatch, X, r, "plain", k, metric)
+
+
+@pytest.mark.parametrize("n,loop", [(65_535, "plain"), (65_536, "screened")])
+def test_fused_float64_screen_threshold(gpu, monkeypatch, n, loop):
+    """MSM_KC_BATCH=0 on the two sides of KSC_MIN_ROWS; the single fit runs with the same knob."""
+    env = {"MSM_KC_BATCH": "0"}
+    X = _rows(n, 10, _F64, seed=41)
+    r = _sharded(monkeypatch, X, 20, env=env)
+    _check(monkeypatch, X, r, loop, 20, env=env)
+
+
+# ---------------------------------------------------------------------------------------------------- batched, float64
+@pytest.mark.parametrize("m", [1, 2, 3, 10, 15, 16])
+def test_batched_float64(gpu, monkeypatch, m):
+    """Every np = ceil(m / 2) instantiation of the batched kernels, odd and even widths, K = 9, 10, 40, on one tile and a
+    bit, on several waves of workgroups and on a grid that strides."""
+    import torch
+    for n in (300, 70_001, KC_MAXBLK * DT + 9_000):
+        Xh = batch_rows(n, m, seed=m * 13 + n % 89)   # (rows around hubs alone give one centre per round at K = 9, 10)
+        X = torch.from_numpy(Xh).cuda()
+        for k in (9, 10, 40):
+            r = _sharded(monkeypatch, X, k)
+            print("batched m=%d n=%d K=%d: stats %s, fallbacks %d" % (m, n, k, r["st"][:3], r["fb"]))
+            _, single = _check(monkeypatch, X, r, "batched", k, Xh=Xh)
+            if n >= 70_001:
+                # one centre per exchange on the same rows: from KSC_MIN_ROWS = 65,536 rows on that is the fused loop with
+                # screened passes, the stronger comparison (another kernel family); below, it would be the plain loop
+                b = _sharded(monkeypatch, X, k, env={"MSM_KC_BATCH": "0"})
+                _assert_loop(b, "screened", n, k)
+                _assert_bit_equal(r, b)
+                _assert_inertia(b["inertia"], b["dist"])
+
+
+# ---------------------------------------------------------------------------------------------------- generic
+GENERIC_SMALL = [(_F32, 33, False), (_F64, 17, False), (_F32, 36, False), (_F64, 18, False), (_F32, 36, True)]
+
+
+@pytest.mark.parametrize("dtype,m,offset", GENERIC_SMALL,
+                         ids=["%s-%d%s" % (np.dtype(d).name, m, "-offset" if o else "") for d, m, o in GENERIC_SMALL])
+def test_generic_rows_past_fc(gpu, monkeypatch, dtype, m, offset):
+    """One feature past the register path (never wide_ok), the first wide_ok widths, and those at an offset address."""
+    X = _rows(3_000, m, dtype, seed=m + 50, offset=offset)
+    r = _sharded(monkeypatch, X, 12)
+    _check(monkeypatch, X, r, "generic", 12)
+
+
+@pytest.mark.parametrize("size", ["T1-", "T1+"])
+@pytest.mark.parametrize("dtype,m", [(_F32, 36), (_F64, 18)], ids=["float32-36", "float64-18"])
+def test_generic_on_both_sides_of_the_wide_grid(gpu, monkeypatch, dtype, m, size):
+    """wide_ok rows where ceil(n / DT) is just under and just over 2 C: the uncut and the cut grid of the wide kernel."""
+    import torch
+    n = _n(size)
+    c2 = 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    assert (-(-n // DT) > c2) == (size == "T1+")
+    X = _rows(n, m, dtype, seed=m + 60)
+    assert X.data_ptr() % 16 == 0
+    r = _sharded(monkeypatch, X, 24, seed=n // 3)
+    _check(monkeypatch, X, r, "generic", 24, seed=n // 3)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_generic_metrics(gpu, monkeypatch, metric):
+    X = _rows(3_000, 40, _F32, seed=71)
+    r = _sharded(monkeypatch, X, 9, metric)
+    _check(monkeypatch, X, r, "generic", 9, metric)
+
+
+# ---------------------------------------------------------------------------------------------------- the three loops on special rows
+LOOPS = {"fused": (_F32, 10, 12, "plain"), "batched": (_F64, 10, 12, "batched"), "generic": (_F32, 40, 9, "generic")}
+
+
+@pytest.mark.parametrize("kind", list(LOOPS))
+def test_row_offset_beyond_int32(gpu, monkeypatch, kind):
+    """A world of one whose shard starts at global row 5,000,000,011: the ids move by the offset, nothing else moves."""
+    dtype, m, k, loop = LOOPS[kind]
+    X = _rows(3_001, m, dtype, seed=81)
+    a = _sharded(monkeypatch, X, k, seed=ROW_OFFSET + 3, row_offset=ROW_OFFSET)
+    _assert_loop(a, loop, 3_001, k)
+    b = _sharded(monkeypatch, X, k, seed=3)
+    _check(monkeypatch, X, b, loop, k)
+    assert min(a["ids"]) >= ROW_OFFSET
+    _assert_bit_equal(a, b, row_offset=ROW_OFFSET)
+    assert a["inertia"] == b["inertia"]
+
+
+@pytest.mark.parametrize("kind", list(LOOPS))
+def test_equal_rows_the_lower_row_wins(gpu, monkeypatch, kind):
+    dtype, m, k, loop = LOOPS[kind]
+    import torch
+    Xh, later = tie_rows(m, dtype)
+    X = torch.from_numpy(Xh).cuda()
+    r = _sharded(monkeypatch, X, k)
+    _check(monkeypatch, X, r, loop, k, Xh=Xh)
+    assert r["ids"][1] == 40 and r["ids"][2] == 300, r["ids"]
+    assert not set(r["ids"]) & set(later + [950, 600]), r["ids"]
+
+
+@pytest.mark.parametrize("kind", list(LOOPS))
+def test_constant_matrix(gpu, monkeypatch, kind):
+    """Every distance is 0 after the first pass: numpy's argmax is row 0, for every further centre."""
+    import torch
+    dtype, m, k, loop = LOOPS[kind]
+    X = torch.full((500, m), 1.5, dtype=torch.float32 if dtype == _F32 else torch.float64, device="cuda")
+    r = _sharded(monkeypatch, X, k)
+    _check(monkeypatch, X, r, "batched1" if loop == "batched" else loop, k)
+    assert r["ids"] == [3] + [0] * (k - 1)
+
+
+@pytest.mark.parametrize("dtype,m,loop", [(_F32, 5, "plain"), (_F64, 5, "plain"), (_F32, 40, "generic")],
+                         ids=["fused-float32", "fused-float64", "generic"])
+def test_as_many_centres_as_rows(gpu, monkeypatch, dtype, m, loop):
+    X = _rows(7, m, dtype, seed=95)
+    r = _sharded(monkeypatch, X, 7)
+    _check(monkeypatch, X, r, loop, 7)
+    assert sorted(r["ids"]) == list(range(7))
+
+
+@pytest.mark.parametrize("kind", list(LOOPS))
+def test_non_finite_rows(gpu, monkeypatch, kind):
+    """One NaN row and one +inf row.  `d < cur` is false for NaN, so such a row keeps distance inf and is chosen again;
+    the oracle is the judge."""
+    dtype, m, k, loop = LOOPS[kind]
+    X = _rows(2_000, m, dtype, seed=97)
+    X[700, 1] = float("nan")
+    X[1_300, 0] = float("inf")
+    r = _sharded(monkeypatch, X, k)
+    _check(monkeypatch, X, r, "batched1" if loop == "batched" else loop, k)
+    assert np.isinf(r["dist"][700]) and np.isinf(r["dist"][1_300]) and not np.isnan(r["dist"]).any()
+
+
+@pytest.mark.parametrize("dtype,loop", [(_F32, "plain"), (_F64, "batched")], ids=["float32-fused", "float64-batched"])
+def test_more_centres_than_the_pruning_table(gpu, monkeypatch, dtype, loop):
+    """K = 2,100 > KC_PRUNE_MAX: the sharded fit and the single fit, each against the oracle."""
+    n, m, k = 6_000, 3, 2_100
+    X = _rows(n, m, dtype, seed=99)
+    r = _sharded(monkeypatch, X, k)
+    Xh, single = _check(monkeypatch, X, r, loop, k)
+    assert r["labels"].max() >= 2048
+    o = _oracle_fit(Xh, k, "euclidean", 3)
+    assert single["ids"] == o["ids"]
+    assert np.array_equal(single["labels"], o["labels"]) and np.array_equal(single["dist"], o["dist"])
+    _assert_inertia(single["inertia"], single["dist"])
+
+
+# ---------------------------------------------------------------------------------------------------- estimator level
+@pytest.mark.parametrize("dtype", [_F32, _F64], ids=["float32", "float64"])
+def test_estimator_forced_through_the_sharded_fit(gpu, monkeypatch, dtype):
+    """KCenters with _force_sharded on three separately allocated device sequences equals the default fit."""
+    from msmbuilder_amd import KCenters
+    from msmbuilder_amd.cluster.kcenters import _KCenters
+    _set_knobs(monkeypatch, None)
+    seqs = [_rows(n, 10, dtype, seed=200 + n) for n in (1_500, 700, 2_300)]
+    ref = KCenters(n_clusters=12, random_state=3).fit(seqs)
+    assert _KCenters._force_sharded is False
+    monkeypatch.setattr(_KCenters, "_force_sharded", True)
+    kc = KCenters(n_clusters=12, random_state=3).fit(seqs)
+    st, _ = _stats()
+    assert st[0] == 4_500 and ((st[1] == 2 and 0 < st[2] < 10) if dtype == _F64 else (st[1] == 12 and st[2] == 0)), st
+    pred = kc.predict(seqs)
+    monkeypatch.undo()
+    assert _KCenters._force_sharded is False
+    assert kc.cluster_ids_ == ref.cluster_ids_
+    assert np.array_equal(np.asarray(kc.cluster_centers_), np.asarray(ref.cluster_centers_))
+    for s, a, b, da, db, p in zip(seqs, kc.labels_, ref.labels_, kc.distances_, ref.distances_, pred):
+        assert len(a) == len(s)
+        assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
+        assert np.array_equal(da.cpu().numpy(), db.cpu().numpy())
+        assert np.array_equal(np.asarray(p.cpu().numpy() if hasattr(p, "cpu") else p), a.cpu().numpy())
+    _assert_inertia(kc.inertia_, np.concatenate([d.cpu().numpy() for d in kc.distances_]))
+
+
+# ---------------------------------------------------------------------------------------------------- two ranks on one GPU
+_WORKER = r'''
+import ctypes as C, math, os, sys, warnings
+import numpy as np
+sys.path.insert(0, {root!r})
+sys.path.insert(0, {tests!r})
+import torch
+import torch.distributed as dist
+from msmbuilder_amd import KCenters, parallel, _lib
+from kcenters_sharded_cases import TWO_RANK_CASES, two_rank_rows
+rank, world, local = parallel.init_from_env(backend="gloo")
+_lib.ensure_device(0)
+warnings.simplefilter("ignore")
+
+
+def stats():
+    st = (C.c_int64 * 5)()
+    _lib.check(_lib.lib().msm_kcenters_last_stats(st))
+    return list(st)
+
+
+for index, (name, dtype, m, metric, k, n, cut, state, loop) in enumerate(TWO_RANK_CASES):
+    X = two_rank_rows(index)
+    lo, hi = (0, cut) if rank == 0 else (cut, n)
+    block = X[lo:hi]
+    before = stats()
+    kc = KCenters(n_clusters=k, metric=metric, random_state=state).fit([block])
+    st = stats()
+    assert parallel._lib_comm_kind == "host", parallel._lib_comm_kind
+    if loop == "generic" or len(block) == 0:           # (a rank without rows runs the generic kernels)
+        assert st == before and st[0] != len(block), (name, before, st)
+    elif loop == "plain":
+        assert st[0] == len(block) and st[1] == k and st[2] == 0, (name, st)
+    else:
+        assert st[0] == len(block) and st[1] == 2 and 0 < st[2] < k - 2, (name, st)
+        both = torch.tensor([int(st[2])]); dist.all_reduce(both, op=dist.ReduceOp.MAX)
+        assert int(both[0]) == st[2], name                # every rank ran the same rounds
+    os.environ["MSMBUILDER_AMD_PARALLEL"] = "0"
+    ref = KCenters(n_clusters=k, metric=metric, random_state=state).fit([X])
+    os.environ["MSMBUILDER_AMD_PARALLEL"] = "1"
+    ids = kc.cluster_ids_
+    assert ids == ref.cluster_ids_, (name, ids, ref.cluster_ids_)
+    assert kc.cluster_centers_.dtype == ref.cluster_centers_.dtype
+    assert np.array_equal(kc.cluster_centers_, ref.cluster_centers_), name
+    assert np.array_equal(kc.labels_[0].cpu().numpy(), ref.labels_[0][lo:hi]), name
+    assert np.array_equal(kc.distances_[0].cpu().numpy(), ref.distances_[0][lo:hi]), name
+    tot = math.fsum(ref.distances_[0])
+    assert abs(kc.inertia_ - tot) <= n * 2.0 ** -53 * tot, (name, kc.inertia_, tot)
+    # what the rows were built for: the lower twin wins, and the winning shard changes from centre to centre
+    first, twin = (5, 299) if n == 300 else (3, cut + 1)
+    if name.endswith("-seed"):
+        assert ids[0] == 299 and first not in ids, (name, ids)
+    else:
+        assert min(first, twin) in ids and max(first, twin) not in ids, (name, ids)
+        assert n != 300 or ids[1] == 5, (name, ids)
+    if cut > 1 and n - cut > 4:
+        sides = [i >= cut for i in ids]
+        assert sum(a != b for a, b in zip(sides, sides[1:])) >= 4, (name, ids)
+    print("rank", rank, name, "ok", st, flush=True)
+dist.barrier()
+parallel.library_comm_shutdown()
+dist.destroy_process_group()
+print("rank", rank, "all ok")
+'''
+
+
+def test_two_ranks_match_single_process(gpu, tmp_path):
+    """Consecutive row blocks on two ranks (host-callback transport, three processes on the GPU with this one) against the
+    single-process fit of the whole array: the cases of kcenters_sharded_cases.TWO_RANK_CASES."""
+    assert len(TWO_RANK_CASES) == 9
+    script = tmp_path / "worker.py"
+    script.write_text(_WORKER.format(root=ROOT, tests=os.path.join(ROOT, "tests")))
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29641", WORLD_SIZE="2")
+    for key in KNOBS:
+        env.pop(key, None)
+    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), LOCAL_RANK="0"),
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
+    outs, failed = [], None
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=240)[0])
+        except subprocess.TimeoutExpired:
+            failed = "timeout"
+            break
+        if p.returncode != 0:
+            failed = "exit status %d" % p.returncode
+            break
+    if failed:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+        tails = [p.communicate()[0] for p in procs[len(outs):]]
+        pytest.fail("%s\n%s" % (failed, "\n----\n".join(o[-3000:] for o in outs + tails)))
+    for o in outs:
+        assert "all ok" in o, o[-3000:]
