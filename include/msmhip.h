@@ -27,6 +27,8 @@
  *   msm_pdist_* / msm_sumdist_*  libdistance/src/pdist.hpp:4-88, sumdist.hpp:4-44 (via libdistance.pyx:182-226, 273-310)
  *   msm_kcenters_fit_*    cluster/kcenters.py:79-102 (_KCenters.fit's k-pass loop)
  *   msm_regspatial_fit_*  cluster/regularspatial.py:69-81 (_RegularSpatial.fit's per-row loop)
+ *   msm_kmedoids*     cluster/src/kmedoids.cc:74-260 (via _kmedoids.pyx:23-107), with the pdist call in front of it
+ *                     (cluster/kmedoids.py:91, cluster/minibatchkmedoids.py:83)
  *   msm_kmeans_* / msm_mbk_*  sklearn MiniBatchKMeans arithmetic behind
  *                     cluster/__init__.py:67-69 (third-party)
  * The exact reference signatures of libdistance are additionally exported,
@@ -404,6 +406,39 @@ int msm_regspatial_result_f64(msm_idx_t* ids, double* centers);
 /* What the last regular spatial fit of this process did: out4 = {blocks run, survivors handed to the resolve step,
  * resolve rounds (= centres chosen), growths of the centre list}. */
 int msm_regspatial_last_stats(msm_idx_t* out4);
+
+/* K-medoids clustering on a condensed distance matrix (cluster/src/kmedoids.cc:74-260): npass passes of {medoid of
+ * every cluster = its lowest-index member of lowest summed distance to the other members; every element to the first
+ * cluster, in cluster order, whose medoid is strictly nearest; total = sum of those distances} until the total stops
+ * falling or a periodically saved assignment comes back.  Every sum is added in the reference's order by one lane, so
+ * clusterid, error and ifound are the reference's bit for bit.  The matrix stays on the device: a handful of launches and
+ * ONE host synchronisation per iteration, or -- n <= 180, the matrix fits one workgroup's LDS -- one launch per pass
+ * (MSM_KMEDOIDS_SMALL=0: always the general path).
+ *   dmat: n(n-1)/2 doubles, entry (i, j), i < j, at msm_kmedoids_condensed_index(i, j, n); follows on_device.
+ *   init (host, max(npass, 1) x n): the assignment each pass starts from, values in [0, K), no cluster empty.  npass = 0
+ *   runs one pass from the caller's assignment; for npass >= 1 the caller draws the random assignments the reference draws
+ *   inside its loop (they do not depend on the data).
+ *   clusterid (host, n, out): the medoid's element index for every element; *error: the best pass's total; *ifound: how
+ *   often it was found.  For npass <= 1 the reference works in place and compares labels with medoid ids: when every
+ *   label equals its medoid's index, *error stays DBL_MAX and *ifound is 0 (kept).
+ * MSM_ERR_INVALID: K < 1, K > n, npass < 0, an init value outside [0, K), an empty cluster in init (the reference reads an
+ * unset medoid there), a negative entry of dmat (distances are >= 0: the medoid selection orders the summed costs by their
+ * bit patterns); MSM_ERR_METRIC: null / unknown metric; MSM_ERR_NONFINITE: a NaN or infinite distance or sum (the
+ * reference's loop is not defined for them).  On an error nothing is written.
+ * msm_kmedoids_fit_*: pdist of the (indexed) rows of X (n x m; X and X_indices follow on_device) into a device buffer of
+ * the library, then the same loop: the matrix never leaves HBM. */
+msm_idx_t msm_kmedoids_condensed_index(msm_idx_t i, msm_idx_t j, msm_idx_t n);   /* i != j; no device needed */
+int msm_kmedoids(const double* dmat, msm_idx_t n, msm_idx_t K, msm_idx_t npass, const msm_idx_t* init,
+                 msm_idx_t* clusterid, double* error, msm_idx_t* ifound, int on_device);
+int msm_kmedoids_fit_f32(const float* X, msm_idx_t n, msm_idx_t m, const char* metric, const msm_idx_t* X_indices,
+                         msm_idx_t n_X_indices, msm_idx_t K, msm_idx_t npass, const msm_idx_t* init,
+                         msm_idx_t* clusterid, double* error, msm_idx_t* ifound, int on_device);
+int msm_kmedoids_fit_f64(const double* X, msm_idx_t n, msm_idx_t m, const char* metric, const msm_idx_t* X_indices,
+                         msm_idx_t n_X_indices, msm_idx_t K, msm_idx_t npass, const msm_idx_t* init,
+                         msm_idx_t* clusterid, double* error, msm_idx_t* ifound, int on_device);
+/* What the last successful k-medoids call of this process did: out4 = {passes run, iterations of the last pass,
+ * path (1: one-workgroup, 0: general), snapshots taken in the last pass}. */
+int msm_kmedoids_last_stats(msm_idx_t* out4);
 
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works

@@ -116,6 +116,11 @@ def _declare(lib):
         f("msm_regspatial_fit_" + sfx, C.c_int, _p, _i64, _i64, C.c_char_p, C.c_double, _i64, C.c_int, _i64p)
         f("msm_regspatial_result_" + sfx, C.c_int, _p, _p)
     f("msm_regspatial_last_stats", C.c_int, _i64p)
+    f("msm_kmedoids_condensed_index", _i64, _i64, _i64, _i64)
+    f("msm_kmedoids", C.c_int, _p, _i64, _i64, _i64, _p, _p, _f64p, _i64p, C.c_int)
+    for sfx in ("f32", "f64"):
+        f("msm_kmedoids_fit_" + sfx, C.c_int, _p, _i64, _i64, C.c_char_p, _p, _i64, _i64, _i64, _p, _p, _f64p, _i64p, C.c_int)
+    f("msm_kmedoids_last_stats", C.c_int, _i64p)
     f("msm_tica_export_sums", C.c_int, _p, _p, _p)
     f("msm_tica_reduce", C.c_int, _p, C.c_double, _i64, _p, _p, _p, _p)
     f("msm_tica_backsolve", C.c_int, _p, _p, _i64, _p)

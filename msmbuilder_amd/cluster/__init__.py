@@ -2,7 +2,10 @@
 from .base import MultiSequenceClusterMixin
 from .kcenters import KCenters
 from .kmeans import KMeans
+from .kmedoids import KMedoids
 from .minibatchkmeans import MiniBatchKMeans
+from .minibatchkmedoids import MiniBatchKMedoids
 from .regularspatial import RegularSpatial
 
-__all__ = ['KCenters', 'KMeans', 'MiniBatchKMeans', 'RegularSpatial', 'MultiSequenceClusterMixin']
+__all__ = ['KCenters', 'KMeans', 'KMedoids', 'MiniBatchKMeans', 'MiniBatchKMedoids', 'RegularSpatial',
+           'MultiSequenceClusterMixin']

@@ -732,6 +732,40 @@ int kcenters_impl(const T* X, msm_idx_t n, msm_idx_t m, msm_idx_t K, const char*
     return MSM_OK;
 }
 
+// Stages the inputs of a pdist (host rows / indices are uploaded to the PS_X / PS_IDX slots, device ones used in place) and
+// queues the kernel that writes the nn(nn-1)/2 condensed distances to the DEVICE buffer dout.  Nothing is synchronised.
+// Shared by pdist_impl and the k-medoids fit (kmedoids.hip), whose matrix never leaves HBM.
+template <typename T>
+int pdist_queue(const T* X, int mid, msm_idx_t n, msm_idx_t m, const msm_idx_t* X_indices, msm_idx_t nn, int on_device,
+                double* dout)
+{
+    int rc;
+    DevBuf &dX = pool(PS_X), &dIdx = pool(PS_IDX);
+    PdArgs P;
+    memset(&P, 0, sizeof(P));
+    P.n = nn;
+    P.m = m;
+    P.out = dout;
+    if (on_device) {
+        P.X = X;
+        P.X_indices = X_indices;
+    } else {
+        if ((rc = dX.reserve((size_t)n * m * sizeof(T)))) return rc;
+        if ((rc = h2d_bulk(dX.p, X, (size_t)n * m * sizeof(T)))) return rc;
+        P.X = dX.p;
+        if (X_indices) {
+            if ((rc = dIdx.reserve((size_t)nn * sizeof(msm_idx_t)))) return rc;
+            MSM_HIP_CHECK(hipMemcpyAsync(dIdx.p, X_indices, (size_t)nn * sizeof(msm_idx_t), hipMemcpyHostToDevice, stream()));
+            P.X_indices = dIdx.as<msm_idx_t>();
+        }
+    }
+    launch_pd<T, 0>(mid, (int)std::min<long long>(nn - 1, 4096), P);
+    MSM_HIP_CHECK(hipGetLastError());
+    return MSM_OK;
+}
+template int pdist_queue<float>(const float*, int, msm_idx_t, msm_idx_t, const msm_idx_t*, msm_idx_t, int, double*);
+template int pdist_queue<double>(const double*, int, msm_idx_t, msm_idx_t, const msm_idx_t*, msm_idx_t, int, double*);
+
 template <typename T>
 int pdist_impl(const T* X, const char* metric, msm_idx_t n, msm_idx_t m, const msm_idx_t* X_indices,
                msm_idx_t n_idx, double* out, int on_device)
@@ -744,31 +778,15 @@ int pdist_impl(const T* X, const char* metric, msm_idx_t n, msm_idx_t m, const m
     if (nn < 2) return MSM_OK;
     if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
     int rc;
-    DevBuf &dX = pool(PS_X), &dIdx = pool(PS_IDX), &dOut = pool(PS_OUT);
     const size_t npairs = (size_t)nn * (size_t)(nn - 1) / 2;
-    PdArgs P;
-    memset(&P, 0, sizeof(P));
-    P.n = nn;
-    P.m = m;
-    if (on_device) {
-        P.X = X;
-        P.X_indices = X_indices;
-        P.out = out;
-    } else {
-        if ((rc = dX.reserve((size_t)n * m * sizeof(T)))) return rc;
-        if ((rc = h2d_bulk(dX.p, X, (size_t)n * m * sizeof(T)))) return rc;
-        P.X = dX.p;
-        if (X_indices) {
-            if ((rc = dIdx.reserve((size_t)nn * sizeof(msm_idx_t)))) return rc;
-            MSM_HIP_CHECK(hipMemcpyAsync(dIdx.p, X_indices, (size_t)nn * sizeof(msm_idx_t), hipMemcpyHostToDevice, stream()));
-            P.X_indices = dIdx.as<msm_idx_t>();
-        }
+    double* dout = out;
+    if (!on_device) {
+        DevBuf& dOut = pool(PS_OUT);
         if ((rc = dOut.reserve(npairs * sizeof(double)))) return rc;
-        P.out = dOut.as<double>();
+        dout = dOut.as<double>();
     }
-    launch_pd<T, 0>(mid, (int)std::min<long long>(nn - 1, 4096), P);
-    MSM_HIP_CHECK(hipGetLastError());
-    if (!on_device && (rc = d2h_bulk(out, P.out, npairs * sizeof(double)))) return rc;
+    if ((rc = pdist_queue<T>(X, mid, n, m, X_indices, nn, on_device, dout))) return rc;
+    if (!on_device && (rc = d2h_bulk(out, dout, npairs * sizeof(double)))) return rc;
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
     return MSM_OK;
 }

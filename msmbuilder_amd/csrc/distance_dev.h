@@ -175,4 +175,9 @@ struct PairArgs {
 bool launch_small3_f32(int metric, int grid, const PairArgs& P);
 bool launch_small3_f64(int metric, int grid, const PairArgs& P);
 
+// distance.hip: stage a pdist's inputs and queue its kernel into a device buffer (pdist_impl and kmedoids.hip share it)
+template <typename T>
+int pdist_queue(const T* X, int mid, msm_idx_t n, msm_idx_t m, const msm_idx_t* X_indices, msm_idx_t nn, int on_device,
+                double* dout);
+
 }  // namespace msm
