@@ -29,6 +29,8 @@
  *   msm_regspatial_fit_*  cluster/regularspatial.py:69-81 (_RegularSpatial.fit's per-row loop)
  *   msm_kmedoids*     cluster/src/kmedoids.cc:74-260 (via _kmedoids.pyx:23-107), with the pdist call in front of it
  *                     (cluster/kmedoids.py:91, cluster/minibatchkmedoids.py:83)
+ *   msm_linkage* / msm_landmark_*  cluster/agglomerative.py:183-221 (pdist, the fastcluster linkage call, the loop over
+ *                     all pairs) and :248-273 (predict: cdist + pooling per cluster)
  *   msm_kmeans_* / msm_mbk_*  sklearn MiniBatchKMeans arithmetic behind
  *                     cluster/__init__.py:67-69 (third-party)
  * The exact reference signatures of libdistance are additionally exported,
@@ -439,6 +441,62 @@ int msm_kmedoids_fit_f64(const double* X, msm_idx_t n, msm_idx_t m, const char* 
 /* What the last successful k-medoids call of this process did: out4 = {passes run, iterations of the last pass,
  * path (1: one-workgroup, 0: general), snapshots taken in the last pass}. */
 int msm_kmedoids_last_stats(msm_idx_t* out4);
+
+/* Landmark agglomerative clustering (cluster/agglomerative.py).
+ *
+ * msm_linkage: agglomerative linkage of n observations from their condensed float64 distance matrix (entry (i, j), i < j,
+ * at n*i - i(i+1)/2 + j - 1 - i; follows on_device), method "single" | "complete" | "average" | "ward".  Plain
+ * global-minimum agglomeration on a square float64 working copy in device memory (8 n^2 bytes, released on return):
+ * each of the n - 1 steps merges the active pair of lowest distance -- at a tie the lowest row slot, then the lowest
+ * column slot, i < j --, the merged cluster keeps slot j, and every other active slot k gets, in float64 with sizes
+ * converted to double and every product and sum evaluated left to right as written (a = D[i,k], b = D[j,k]),
+ *   single    min(a, b)                  complete   max(a, b)              average   (ni*a + nj*b)/(ni + nj)
+ *   ward      t = 1.0/(ni + nj + nk);  sqrt((ni + nk)*t*a*a + (nj + nk)*t*b*b - nk*t*dij*dij).
+ * A step is three launches (select, update, refresh of the cached nearest neighbours); all steps are queued and the host
+ * synchronises once, to read Z.
+ *   Z (host, (n - 1) x 4 doubles, out): scipy's convention -- row s = (id_a < id_b, height, size of the new cluster),
+ *   observations are 0 .. n-1, the cluster made at step s is n + s, rows in merge order.
+ * MSM_ERR_INVALID: n < 2, an unknown or null method, a null pointer; MSM_ERR_NONFINITE: a NaN or infinite entry of dmat,
+ * or a merged distance that is not finite (overflow; ward's square root of a negative number for distances that are not
+ * Euclidean); MSM_ERR_HIP: the working copy could not be allocated.  On an error nothing is written.
+ * msm_linkage_fit_*: pdist of the (indexed) rows of X (n x m; X and X_indices follow on_device) into a device buffer of
+ * the library, then the same loop; MSM_ERR_METRIC for a null / unknown metric.  The matrix is kept for
+ * msm_landmark_within(dmat = NULL) until the next msm_linkage_fit_*; one above 64 MiB is released by that call.
+ * msm_linkage_plan: out2 = {threads per workgroup, rows one workgroup of the refresh launch covers}. */
+int msm_linkage(const double* dmat, msm_idx_t n, const char* method, double* Z, int on_device);
+int msm_linkage_fit_f32(const float* X, msm_idx_t n, msm_idx_t m, const char* metric, const msm_idx_t* X_indices,
+                        msm_idx_t n_X_indices, const char* method, double* Z, int on_device);
+int msm_linkage_fit_f64(const double* X, msm_idx_t n, msm_idx_t m, const char* metric, const msm_idx_t* X_indices,
+                        msm_idx_t n_X_indices, const char* method, double* Z, int on_device);
+int msm_linkage_plan(msm_idx_t* out2);
+/* out[c] (host, K doubles) = sum of d(i, j)^2 over the pairs i < j with labels[i] == labels[j] == c
+ * (agglomerative.py:191-196).  Summation order, fixed: for row i, thread t of 256 adds its columns i+1+t, i+1+t+256, ...
+ * in ascending order and the 256 partial sums are added in a binary tree; a cluster's row sums are added the same way.
+ * No floating-point atomics: two runs give the same bits.
+ *   dmat: condensed, n(n-1)/2 doubles, follows on_device; NULL = the matrix of the last msm_linkage_fit_* (MSM_ERR_STATE
+ *   when there is none of n elements).  labels (host, n): values in [0, K) (MSM_ERR_INVALID otherwise). */
+int msm_landmark_within(const double* dmat, msm_idx_t n, const msm_idx_t* labels, msm_idx_t K, double* out, int on_device);
+/* Pooled landmark predict (agglomerative.py:248-273), one fused kernel: the n x L distance matrix is never formed.
+ *   X (n x m, follows on_device); landmarks (host, L x m, X's element type), permuted so that cluster c's landmarks are
+ *   rows offsets[c] .. offsets[c+1]-1 (offsets: host, K + 1, from 0 to L, not decreasing; a cluster may be empty);
+ *   intra (host, K; needed for "ward"): msm_landmark_within's sums; pooling "single" | "complete" | "average" | "ward".
+ * Every distance is msm_cdist_*'s bit for bit.  A cluster's pooled value: single = min, complete = max (both keep a NaN
+ * once met, like numpy's), average = sum / cnt, ward = (cnt * sum of d*d - intra[c]) / (cnt*(cnt+1)/2), where the two
+ * sums start at 0.0 and add ONE TERM PER LANDMARK IN ASCENDING (permuted) LANDMARK INDEX.  The label is a running strict
+ * < over the clusters in ascending id from (+inf, 0); clusters without a landmark are skipped, a NaN value never wins, a
+ * row whose values are all NaN or +inf gets label 0.
+ *   labels (n, int64) and pooled (n doubles, nullable: the winning value) follow on_device; *negative (host) = 1 when
+ *   some ward value was negative.
+ * MSM_ERR_INVALID: unknown pooling ("linkage ... is not supported"), bad shapes or offsets; MSM_ERR_METRIC.
+ * msm_landmark_predict_plan: out4 = {rows per workgroup, landmarks per LDS tile, features per chunk (m: whole landmarks),
+ * 1 when the rows are held in registers} for rows of m elements of elem_size (4 | 8) bytes. */
+int msm_landmark_predict_f32(const float* X, msm_idx_t n, msm_idx_t m, const float* landmarks, msm_idx_t L,
+                             const msm_idx_t* offsets, msm_idx_t K, const double* intra, const char* metric,
+                             const char* pooling, msm_idx_t* labels, double* pooled, int* negative, int on_device);
+int msm_landmark_predict_f64(const double* X, msm_idx_t n, msm_idx_t m, const double* landmarks, msm_idx_t L,
+                             const msm_idx_t* offsets, msm_idx_t K, const double* intra, const char* metric,
+                             const char* pooling, msm_idx_t* labels, double* pooled, int* negative, int on_device);
+int msm_landmark_predict_plan(msm_idx_t m, int elem_size, msm_idx_t* out4);
 
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works

@@ -8,6 +8,7 @@ __version__ = "0.1.0"
 
 from . import libdistance  # noqa: F401
 from . import preprocessing  # noqa: F401
-from .cluster import KCenters, KMeans, KMedoids, MiniBatchKMeans, MiniBatchKMedoids, RegularSpatial  # noqa: F401
+from .cluster import (KCenters, KMeans, KMedoids, LandmarkAgglomerative, MiniBatchKMeans, MiniBatchKMedoids,  # noqa: F401
+                      RegularSpatial)
 from .decomposition import tICA  # noqa: F401
 from .msm import MarkovStateModel  # noqa: F401

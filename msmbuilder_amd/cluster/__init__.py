@@ -1,4 +1,5 @@
 """Clusterers of the MSMBuilder hot path on MI355X (reference: msmbuilder/cluster/__init__.py)."""
+from .agglomerative import LandmarkAgglomerative
 from .base import MultiSequenceClusterMixin
 from .kcenters import KCenters
 from .kmeans import KMeans
@@ -7,5 +8,5 @@ from .minibatchkmeans import MiniBatchKMeans
 from .minibatchkmedoids import MiniBatchKMedoids
 from .regularspatial import RegularSpatial
 
-__all__ = ['KCenters', 'KMeans', 'KMedoids', 'MiniBatchKMeans', 'MiniBatchKMedoids', 'RegularSpatial',
-           'MultiSequenceClusterMixin']
+__all__ = ['KCenters', 'KMeans', 'KMedoids', 'LandmarkAgglomerative', 'MiniBatchKMeans', 'MiniBatchKMedoids',
+           'RegularSpatial', 'MultiSequenceClusterMixin']
