@@ -185,6 +185,24 @@ int msm_tica_last_img_fused(msm_tica_t* h, int* flag);
  * multiply kernel (round 6, the carried pack: whole 256-feature panels, 16-byte aligned rows, more than one super-chunk;
  * MSM_TICA_IMG_CARRY=0 disables): the packets, and hence the accumulators, are the pre-pass kernel's bit for bit. */
 int msm_tica_last_img_carried(msm_tica_t* h, int* flag);
+/* What an accumulation launches -- the library's one dispatch (tica_plan, csrc/tica_plan.h), for tests to ask.
+ * msm_tica_plan is pure (works with no device visible) and plans whole trajectories: geom[MSM_TICA_GEOM_INTS] is a handle's
+ * geometry {F, lag, mode, T, ntiles, S32, S64, sym, ntiles_sym, sym_cohorts, sym_grid, S_sym, symw, symw_var, symw_KS, symw_S,
+ * symw64, symw_S64, img_on, T2, ntile2, S_img, img_grid, have_fold, shift_on}; ptr_aligned16: bit 0 = every trajectory longer
+ * than the lag starts on a 16-byte boundary, bit 1 = the skipped ones do too; dims_aligned4: n_features % 4 == 0 && ld % 4 == 0; fold_switch / fused_switch: the
+ * values of MSM_TICA_FOLD / MSM_TICA_IMG_FUSED (-1: unset).  out[MSM_TICA_PLAN_INTS] = {path (MSM_TICA_PATH_*), flavour
+ * (MSM_TICA_FL_* bits), frames per K-step, cohorts S, workgroups G, remainder cohort, frames per chunk kc, remainder workgroups,
+ * remainder rounds, pair semantics, shifted, folded column sums, kflush, cohort pacing, single (one trajectory, no chunk
+ * table), owned frames, valid trajectories}.  MSM_ERR_INVALID for a geometry no handle has (no cohort for an enabled path).
+ * msm_tica_last_plan: out[MSM_TICA_GEOM_INTS + MSM_TICA_PLAN_INTS + 2] = the handle's geometry, the plan of its most recent
+ * accumulation launch, that launch's chunks and -- bf16 image ring -- super-chunks (else 0). */
+enum { MSM_TICA_PATH_NONE = 0, MSM_TICA_PATH_CG64 = 1, MSM_TICA_PATH_CG32 = 2, MSM_TICA_PATH_SYM = 3, MSM_TICA_PATH_SYMW = 4,
+       MSM_TICA_PATH_SYMW64 = 5, MSM_TICA_PATH_IMG_RING = 6, MSM_TICA_PATH_IMG_FUSED = 7 };
+enum { MSM_TICA_FL_EDGE = 1, MSM_TICA_FL_ALIGNED = 2, MSM_TICA_FL_FOLD = 4, MSM_TICA_FL_REM = 8, MSM_TICA_FL_VEC = 16, MSM_TICA_FL_X2 = 32 };
+enum { MSM_TICA_GEOM_INTS = 25, MSM_TICA_PLAN_INTS = 17 };
+int msm_tica_plan(const int* geom, int dtype_bytes, msm_idx_t ld, const msm_idx_t* n_rows, msm_idx_t n_seq, int ptr_aligned16,
+                  int dims_aligned4, int fold_switch, int fused_switch, long long* out);
+int msm_tica_last_plan(msm_tica_t* h, long long* out);
 /* profiling: {shader-clock start, end, 100 MHz wall-clock start, end} of workgroup 0 of that launch */
 int msm_tica_debug_clocks(msm_tica_t* h, long long* out4);
 /* profiling builds (csrc built with -DMSM_TICA_PROFILE) only: out64[8 + 8*slot + i] = shader cycles wave 0 of

@@ -22,9 +22,11 @@
 #include "tica_img_dev.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <vector>
 
+#include "tica_plan.h"         // TicaGeom / TicaLaunch / TicaPlan and tica_plan: which kernel a launch takes, decided once
 #include "tica_common_dev.h"   // constants, chunk / argument structs and block-id helpers shared by the tICA kernels
 #include <functional>
 
@@ -39,16 +41,34 @@
 
 using namespace msm;
 
+// a chunk table on the device, with the key of what it was built from
+struct ChunkTable {
+    DevBuf buf;
+    unsigned long long key = 0;   // 0: not to be found again
+    long long total = -1, n = 0;  // frames of the keyed launch (a second guard), chunks
+    bool hit(unsigned long long k, long long t) const { return k != 0 && key == k && total == t; }
+    const TicaChunk* chunks() const { return static_cast<const TicaChunk*>(buf.p); }
+    int upload(const std::vector<TicaChunk>& tab, unsigned long long k, long long t)
+    {
+        key = 0;
+        int rc = buf.reserve(tab.size() * sizeof(TicaChunk));
+        if (rc) return rc;
+        MSM_HIP_CHECK(hipMemcpyAsync(buf.p, tab.data(), tab.size() * sizeof(TicaChunk), hipMemcpyHostToDevice, stream()));
+        MSM_HIP_CHECK(hipStreamSynchronize(stream()));  // `tab` is pageable host memory
+        key = k;
+        total = t;
+        n = (long long)tab.size();
+        return MSM_OK;
+    }
+};
+
 struct msm_tica {
-    int F = 0, lag = 0, mode = 0, T = 0, ntiles = 0;
-    int S32 = 0, S64 = 0, S = 0, G = 0;  // cohorts per kernel flavour; S = max (slab count), G = S * ntiles
-    int sym = 0, ntiles_sym = 0, S_sym = 0;                // symmetric fp32 kernel: upper tiles, slab / column-sum ROWS (cohorts, + 1 with a remainder cohort)
-    int sym_cohorts = 0, sym_grid = 0;                     // ... whole cohorts, workgroups of a launch (sym_grid > sym_cohorts * ntiles_sym: remainder cohort)
+    TicaGeom g{};               // what create decided and tica_plan reads (tica_plan.h)
+    int S = 0, G = 0;           // C/G slabs: S = max(S32, S64) cohorts, G = S * ntiles
     double* slabs_sym = nullptr;                           // [S_sym * ntiles_sym][2][TM*TM]: H and D blocks
-    // whole-matrix sum/difference kernel (tica_symw_dev.h; fp32 mode, F <= 256): variant (SymwA ..), its padded width /
-    // group width / interleave, workgroups of a launch (= slab rows), slabs [symw_S][2][FP*FP], rows in use since the last reset
-    int symw = 0, symw_var = 0, symw_FP = 0, symw_W = 0, symw_IL = 0, symw_KS = 0, symw_S = 0, symw_used = 0;
-    int symw64 = 0, symw_S64 = 0;   // ... float64 rows take the same variant on doubles (F <= 128); its resident workgroups
+    // whole-matrix sum/difference kernel (tica_symw_dev.h): the variant's padded width / group width / interleave,
+    // slabs [symw_S][2][FP*FP], rows in use since the last reset
+    int symw_FP = 0, symw_W = 0, symw_IL = 0, symw_used = 0;
     double* slabs_w = nullptr;
     double* slabs = nullptr;    // [G][TM*TM]
     double* base = nullptr;     // packed [2FF+2F] imported state
@@ -60,7 +80,7 @@ struct msm_tica {
     unsigned* cosync = nullptr; // [S] cohort pacing counters
     float* shift = nullptr;     // [F] reference row r of the mean shift (fp32 / bf16 kernels); valid once have_shift
     double* shsum = nullptr;    // [3F] raw column sums [A | B | W] of everything accumulated under the shift
-    bool shift_on = true, have_shift = false;
+    bool have_shift = false;
     double* fold = nullptr;     // folded column sums: [S_sym][F] per-cohort sums of the left frames | [FOLD_NB][F] sample partials | [F] zeros
     bool last_folded = false;   // the most recent launch took the folded path
     bool cg_dirty = false;      // the C/G slabs (`slabs`) hold something since the last reset: only then does the export sum them
@@ -71,35 +91,41 @@ struct msm_tica {
     DevBuf colsteps;            // carried pack: [pack steps of a super-chunk][Fp] fp64 column sums of the left frames
     int last_carried = 0;       // the last accumulate packed its later super-chunks inside the multiply (msm_tica_last_img_carried)
     int last_fused = 0;         // the last accumulate ran the fused kernel (msm_tica_last_img_fused)
+    TicaPlan last_plan;         // the plan of the last accumulate, its chunks and (image ring) super-chunks (msm_tica_last_plan)
+    long long last_nchunks = 0, last_super = 0;
     long long n_sh = 0, nw_sh = 0;  // shifted pairs, and the total weight of their Gram terms (2 n_sh for whole trajectories)
     long long n_obs = 0, n_seq = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the most recent MFMA launch (bf16 image path: the whole pack + multiply pipeline)
     bool timed = false;
-    DevBuf table, table2, staging;
-    // Round 5: the chunk tables of the last launch stay on the device with a key of what they were built from.  Fitting the
+    // The chunk tables of the last launch stay on the device with a key of what they were built from.  Fitting the
     // SAME trajectories again (the bench's steps, partial_fit loops, cross-validated re-fits through a pooled handle) then
     // skips the table build, its upload and the two stream synchronisations that cover the pageable host vectors: ~0.3 ms
     // of idle GPU at 1,000 trajectories, and the host gets to the MFMA launch that much earlier.
-    unsigned long long table_key = 0, table2_key = 0;
-    long long table_n = 0, table2_n = 0, table_img_groups = 0, table_total = -1, table2_total = -1;   // (frames of the keyed launch: a second guard)
+    ChunkTable table, table2;   // the launch's chunks; boundary rows (folded sums) or right frames (segments)
+    long long table_img_groups = 0;
     std::vector<TicaChunk> table_host;   // bf16 image path: the super-chunk loop walks the table on the host
-    int img_on = 0, T2 = 0, ntile2 = 0, S_img = 0, img_grid = 0;  // 256-wide tiles per side, H and D tiles of the upper triangle, whole cohorts, workgroups
+    DevBuf staging;
     double* solve_pin = nullptr; // pinned host staging of the solve's results (one device-to-host copy per solve)
     size_t solve_pin_n = 0;
     DevBuf solve;                // device-resident solve: [A (F*F) | B (F*F) | mu F | D F | E F | scal 4 | part 2*nblk | scale F | Y k*F | vals F | ints]
     bool reduced = false;        // solve.A / solve.B hold the reduced matrix and the Cholesky factor of the current state
-    size_t packed_len() const { return 2 * (size_t)F * F + 2 * (size_t)F + 2; }
+    size_t packed_len() const { return 2 * (size_t)g.F * g.F + 2 * (size_t)g.F + 2; }
+    size_t colbytes() const { return (size_t)NCB * 2 * g.F * sizeof(double); }   // colpart / coltmp
+    size_t sym_slab_bytes() const { return (size_t)g.S_sym * g.ntiles_sym * 2 * TM * TM * sizeof(double); }
 };
 
 namespace {
 
+// Sets a kernel's dynamic-LDS limit and, with `min_slots`, folds its resident workgroups of the whole chip into a running
+// minimum (the flavours of one path must all be resident in one round: the cohorts are sized by the tightest).
 template <typename K>
-int query_slots(K kernel, size_t lds, int* slots)
+int prep_kernel(K kernel, int threads, size_t lds, int* min_slots, int at_least = 1)
 {
+    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (!min_slots) return MSM_OK;
     int occ = 0;
-    MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, NT, lds));
-    if (occ < 1) occ = 1;
-    *slots = occ * num_cus();
+    MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds));
+    *min_slots = std::min(*min_slots, std::max(occ, at_least) * num_cus());
     return MSM_OK;
 }
 
@@ -110,20 +136,38 @@ constexpr size_t IMG_PP_LDS = (size_t)(3 + IMG_LAG) * IMG_SLOT;  // 128 KiB: a r
 constexpr size_t IMG_PP_CARRY_LDS = IMG_PP_LDS + 4 * 8192;       // + the carrier waves' private 8 KiB each: all 160 KiB
 constexpr size_t LDS64 = 2 * 2 * BK64 * P64 * sizeof(double);  // 72 KiB (double-buffered, pitch 144)
 
+// variant id -> its Symw* config (tica_symw_dev.h); ids by width: tica_symw_variant
+template <typename Fn>
+void symw_visit(int var, Fn&& fn)
+{
+    switch (var) {
+        case 0: fn(SymwA{}); break;
+        case 1: fn(SymwB{}); break;
+        case 2: fn(SymwC{}); break;
+        case 3: fn(SymwD{}); break;
+        case 4: fn(SymwE{}); break;
+        case 6: fn(SymwG{}); break;
+        case 7: fn(SymwH{}); break;
+        default: fn(SymwF{}); break;
+    }
+}
+template <typename Cfg>
+constexpr bool symw_has64 = Cfg::FP <= 128;   // float64 rows: the variants of up to 128 features
+
 int tica_zero(msm_tica* h)
 {
-    const size_t FF2 = 2 * (size_t)h->F * h->F + 2 * (size_t)h->F;
+    const TicaGeom& g = h->g;
+    const size_t FF2 = 2 * (size_t)g.F * g.F + 2 * (size_t)g.F;
     MSM_HIP_CHECK(hipMemsetAsync(h->slabs, 0, (size_t)h->G * TM * TM * sizeof(double), stream()));
-    if (h->slabs_sym)
-        MSM_HIP_CHECK(hipMemsetAsync(h->slabs_sym, 0, (size_t)h->S_sym * h->ntiles_sym * 2 * TM * TM * sizeof(double), stream()));
+    if (h->slabs_sym) MSM_HIP_CHECK(hipMemsetAsync(h->slabs_sym, 0, h->sym_slab_bytes(), stream()));
     if (h->slabs_w && h->symw_used > 0)   // (only the rows a launch has touched: 512 slabs of 2 x 192 x 192 doubles are 300 MB)
         MSM_HIP_CHECK(hipMemsetAsync(h->slabs_w, 0, (size_t)h->symw_used * 2 * h->symw_FP * h->symw_FP * sizeof(double), stream()));
     h->symw_used = 0;
     MSM_HIP_CHECK(hipMemsetAsync(h->base, 0, FF2 * sizeof(double), stream()));
-    MSM_HIP_CHECK(hipMemsetAsync(h->colpart, 0, (size_t)NCB * 2 * h->F * sizeof(double), stream()));
-    MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, (size_t)NCB * 2 * h->F * sizeof(double), stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(h->colpart, 0, h->colbytes(), stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, h->colbytes(), stream()));
     MSM_HIP_CHECK(hipMemsetAsync(h->flag, 0, 2 * sizeof(int), stream()));
-    MSM_HIP_CHECK(hipMemsetAsync(h->shsum, 0, 3 * (size_t)h->F * sizeof(double), stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(h->shsum, 0, 3 * (size_t)g.F * sizeof(double), stream()));
     h->have_shift = false;
     h->slabs_dirty = false;
     h->cg_dirty = false;
@@ -131,702 +175,674 @@ int tica_zero(msm_tica* h)
     h->n_sh = h->nw_sh = 0;
     {
         const char* sh_env = getenv("MSM_TICA_SHIFT");  // 0: accumulate raw moments (A/B switch for the tests); read per reset
-        h->shift_on = !(sh_env && atoi(sh_env) == 0);
+        h->g.shift_on = !(sh_env && atoi(sh_env) == 0);
     }
     h->n_obs = 0;
     h->n_seq = 0;
     return MSM_OK;
 }
 
-// A slice of one trajectory: `ptr` is trajectory row `off`, the slice holds n_rows rows, and this
-// call owns the LEFT indices t in [ob, oe) of the lagged pairs (t, t + lag) -- i.e. it adds
-// w_t x_t x_t^T, [t < len - lag] x_t x_{t+lag}^T and the matching column sums for those t only.
-// The slice must reach row min(oe + lag, len) - 1 (the right halo).  Whole trajectory: {n, 0, 0, n}.
-struct SegInfo {
-    long long len, off, ob, oe;
+// ---- one accumulation launch: tica_accumulate_device sequences the steps below, each of which reads the plan -----------
+
+struct Acc {
+    msm_tica* h;
+    const void* const* ptrs;
+    int check_finite;
+    TicaLaunch L;
+    TicaPlan pl;
+    TicaArgs P;                       // arguments of the MFMA kernel (the column-sum passes run on copies)
+    unsigned long long key = 0;       // what the chunk tables are a function of (0: segments, no key)
+    long long img_groups = 0;         // bf16 image path: 8-pair groups of the packed image (whole K-steps per chunk)
+    std::vector<TicaChunk> img_tab;   // ... and its chunk table on the host (cut into ring slots)
+    bool snapshot = false;            // h->snap holds the sum/difference slabs as they were before this launch
+    // virtual row 0 of trajectory s (never dereferenced outside the slice: rows are clamped to [row0, last]), its last addressable row
+    const void* base(long long s, const SegInfo& t) const { return (const char*)ptrs[s] - (ptrdiff_t)t.off * (ptrdiff_t)L.ld * L.dtype_bytes; }
+    long long last(long long s, const SegInfo& t) const { return t.off + L.n_rows[s] - 1; }
 };
 
-// device-resident trajectories only
+// FNV-1a over the pointer / length tables and the launch's parameters (never 0)
+unsigned long long table_key(const Acc& a)
+{
+    unsigned long long hsh = 1469598103934665603ULL;
+    auto mix = [&](unsigned long long v) {
+        for (int b = 0; b < 8; ++b) {
+            hsh ^= (v >> (8 * b)) & 0xffULL;
+            hsh *= 1099511628211ULL;
+        }
+    };
+    mix((unsigned long long)a.L.n_seq);
+    mix((unsigned long long)a.L.dtype_bytes);
+    mix((unsigned long long)a.L.ld);
+    mix((unsigned long long)a.pl.kc);
+    mix((unsigned long long)a.h->g.lag);
+    mix((unsigned long long)a.pl.bk);
+    mix(a.pl.img() ? 1ULL : 0ULL);
+    for (long long s = 0; s < a.L.n_seq; ++s) {
+        mix((unsigned long long)(uintptr_t)a.ptrs[s]);
+        mix((unsigned long long)a.L.n_rows[s]);
+    }
+    return hsh ? hsh : 1ULL;
+}
+
+// Appends rows [b0, b1) of one trajectory to a chunk table, `piece` rows a chunk.  `len` is the length the kernels weigh
+// the rows by (1 << 60: every row counts as a left frame).  img_groups: the image path's running count of 8-pair groups.
+void add_chunks(std::vector<TicaChunk>& tab, const void* base, long long last, long long b0, long long b1, long long piece,
+                long long len, long long* img_groups = nullptr, int lag = 0)
+{
+    for (long long r0 = b0; r0 < b1; r0 += piece) {
+        TicaChunk ch;
+        ch.base = base;
+        ch.row0 = r0;
+        ch.len = len;
+        ch.n = (int)std::min(piece, b1 - r0);
+        ch.pad = 0;
+        ch.last = last;
+        ch.g0 = img_groups ? *img_groups : 0;
+        if (img_groups) *img_groups += ceil_div(std::max<long long>(0, std::min<long long>(ch.n, len - lag - r0)), 32) * 4;
+        tab.push_back(ch);
+    }
+}
+constexpr long long EVERY_ROW = (long long)1 << 60;
+
+// the launch's own chunks: none (one whole trajectory), the table of the last launch, or a new one
+int main_table(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaPlan& pl = a.pl;
+    TicaArgs& P = a.P;
+    if (pl.single) {
+        P.chunks = nullptr;
+        P.single.base = a.ptrs[0];
+        P.single.row0 = 0;
+        P.single.len = a.L.n_rows[0];
+        P.single.last = a.L.n_rows[0] - 1;
+        P.single.n = 0;
+        P.nchunks = ceil_div(a.L.n_rows[0], pl.kc);
+        return MSM_OK;
+    }
+    if (h->table.hit(a.key, pl.total)) {   // the same trajectories as the last launch: its table is still on the device
+        a.img_groups = h->table_img_groups;
+        if (pl.img()) a.img_tab = h->table_host;
+    } else {
+        std::vector<TicaChunk> tab;
+        tab.reserve((size_t)(pl.total / pl.kc + pl.nvalid + 1));
+        for (long long s = 0; s < a.L.n_seq; ++s) {
+            const SegInfo t = a.L.seg(s);
+            if (!a.L.valid(t, h->g.lag)) continue;
+            const long long own = t.oe - t.ob, nch = ceil_div(own, pl.kc);
+            add_chunks(tab, a.base(s, t), a.last(s, t), t.ob, t.oe, ceil_div(ceil_div(own, nch), pl.bk) * pl.bk, t.len,
+                       pl.img() ? &a.img_groups : nullptr, h->g.lag);
+        }
+        int rc = h->table.upload(tab, a.key, pl.total);
+        if (rc) return rc;
+        h->table_img_groups = a.img_groups;
+        if (pl.img()) {
+            if (a.key) h->table_host = tab;
+            a.img_tab.swap(tab);
+        }
+    }
+    P.chunks = h->table.chunks();
+    P.nchunks = h->table.n;
+    return MSM_OK;
+}
+
+int launch_colsum(int dtype_bytes, const TicaArgs& A)
+{
+    if (dtype_bytes == 4)
+        hipLaunchKernelGGL(tica_colsum_kernel<float>, dim3(NCB), dim3(NT), 0, stream(), A);
+    else if (dtype_bytes == 2)
+        hipLaunchKernelGGL(tica_colsum_kernel<__bf16>, dim3(NCB), dim3(NT), 0, stream(), A);
+    else
+        hipLaunchKernelGGL(tica_colsum_kernel<double>, dim3(NCB), dim3(NT), 0, stream(), A);
+    MSM_HIP_CHECK(hipGetLastError());
+    return MSM_OK;
+}
+
+// Reads the non-finite flag (a host wait).  Set: the launch is rejected and the handle left as it was before it -- partials
+// and flag cleared and, `undo_slabs`, the sum/difference slabs restored from the snapshot (or zeroed: nothing was in them).
+int check_finite_flag(Acc& a, bool undo_slabs)
+{
+    msm_tica* h = a.h;
+    int f[2] = {0, 0};
+    MSM_HIP_CHECK(hipMemcpyAsync(f, h->flag, sizeof(f), hipMemcpyDeviceToHost, stream()));
+    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    if (!f[0]) return MSM_OK;
+    if (undo_slabs) {
+        if (a.snapshot)
+            MSM_HIP_CHECK(hipMemcpyAsync(h->slabs_sym, h->snap.p, h->sym_slab_bytes(), hipMemcpyDeviceToDevice, stream()));
+        else
+            MSM_HIP_CHECK(hipMemsetAsync(h->slabs_sym, 0, h->sym_slab_bytes(), stream()));
+    }
+    MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, h->colbytes(), stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(h->flag, 0, sizeof(int), stream()));
+    if (undo_slabs) MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
+}
+
+// mean shift bookkeeping (fp32 / bf16 kernels): the raw column sums of what this launch accumulates under the shift, and
+// -- first shifted launch of the handle, `set_r` -- the reference row r = this launch's column means; then the temporary
+// partials are merged into the handle's
+int shift_and_merge(Acc& a, int set_r)
+{
+    msm_tica* h = a.h;
+    const int F = h->g.F, lag = h->g.lag;
+    if (a.pl.shifted) {
+        const bool segs = a.L.segs != nullptr, pairsem = a.pl.pairsem;
+        long long n_call = 0, nw_call = 0, nmean = 0;
+        for (long long s = 0; s < a.L.n_seq; ++s) {
+            const SegInfo t = a.L.seg(s);
+            if (!a.L.valid(t, lag)) continue;
+            const long long n0 = std::max<long long>(0, std::min<long long>(t.oe, t.len - lag) - t.ob);
+            const long long nt = std::max<long long>(0, t.oe - std::max<long long>(t.ob, lag));
+            n_call += n0;
+            nmean += n0 + nt;
+            nw_call += (segs && !pairsem) ? n0 + nt : 2 * n0;
+        }
+        const int what = !segs ? (SH_A_a | SH_B_b | SH_W_ab) : pairsem ? (SH_A_a | SH_W_a) : (SH_A_a | SH_W_ab);
+        hipLaunchKernelGGL(tica_shift_kernel, dim3((unsigned)ceil_div(F, 64)), dim3(512), 0, stream(), h->coltmp,
+                           h->shsum, h->shift, F, 1.0 / (double)std::max<long long>(1, nmean), set_r, what);
+        MSM_HIP_CHECK(hipGetLastError());
+        h->have_shift = true;
+        h->n_sh += n_call;
+        h->nw_sh += nw_call;
+    }
+    const size_t n = (size_t)NCB * 2 * F;
+    hipLaunchKernelGGL(tica_colmerge_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream(), h->colpart, h->coltmp, n);
+    MSM_HIP_CHECK(hipGetLastError());
+    return MSM_OK;
+}
+
+// 1) column sums + finite check into the temporary partials
+int colsum_pass(Acc& a)
+{
+    msm_tica* h = a.h;
+    int rc = launch_colsum(a.L.dtype_bytes, a.P);
+    if (rc) return rc;
+    if (a.check_finite && (rc = check_finite_flag(a, false))) return rc;
+    if (a.pl.shifted) a.P.shift = h->shift;
+    return shift_and_merge(a, h->have_shift ? 0 : 1);
+}
+
+// 1') folded column sums, the boundary rows: [0, lag) count as left frames only (chunk length "infinite"), [len - lag, len)
+//     as right frames only, so the temporary partials receive a = sum of the first rows | b = sum of the last rows
+int boundary_pass(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaGeom& g = h->g;
+    TicaArgs& P = a.P;
+    int rc = MSM_OK;
+    if (!h->table2.hit(a.key, a.pl.total)) {   // (else the boundary table of the same trajectories: still there)
+        std::vector<TicaChunk> tab;
+        for (long long s = 0; s < a.L.n_seq; ++s) {
+            const long long len = a.L.n_rows[s];
+            if (len <= g.lag) continue;
+            add_chunks(tab, a.ptrs[s], len - 1, 0, g.lag, a.pl.kc, EVERY_ROW);
+            add_chunks(tab, a.ptrs[s], len - 1, len - g.lag, len, a.pl.kc, len);
+        }
+        if ((rc = h->table2.upload(tab, a.key, a.pl.total))) return rc;
+    }
+    TicaArgs Q = P;
+    Q.chunks = h->table2.chunks();
+    Q.nchunks = h->table2.n;
+    if ((rc = launch_colsum(a.L.dtype_bytes, Q))) return rc;
+    if (a.pl.shifted) {
+        if (!h->have_shift) {
+            double* sp = h->fold + (size_t)g.S_sym * g.F;
+            if (a.L.dtype_bytes == 4)
+                hipLaunchKernelGGL(tica_fold_sample_kernel<float>, dim3((unsigned)ceil_div(g.F, 64), FOLD_NB), dim3(256), 0, stream(), P, sp);
+            else
+                hipLaunchKernelGGL(tica_fold_sample_kernel<__bf16>, dim3((unsigned)ceil_div(g.F, 64), FOLD_NB), dim3(256), 0, stream(), P, sp);
+            hipLaunchKernelGGL(tica_fold_setr_kernel, dim3((unsigned)ceil_div(g.F, 256)), dim3(256), 0, stream(), sp, h->shift, g.F);
+            MSM_HIP_CHECK(hipGetLastError());
+        }
+        P.shift = h->shift;
+    }
+    if (a.pl.img()) {
+        if ((rc = h->foldimg.reserve((size_t)P.nchunks * g.F * sizeof(double)))) return rc;   // every word is written by the pre-pass
+    } else {
+        P.colA = h->fold;
+        P.zrow = reinterpret_cast<const float*>(h->fold + (size_t)(g.S_sym + FOLD_NB) * g.F);   // zeroed at creation, never written
+        MSM_HIP_CHECK(hipMemsetAsync(h->fold, 0, (size_t)g.S_sym * g.F * sizeof(double), stream()));
+    }
+    if (a.check_finite && h->slabs_dirty) {   // a rejected launch leaves the state untouched (utils/validation.py:68-74 raises
+        if ((rc = h->snap.reserve(h->sym_slab_bytes()))) return rc;   // before tica.py:401 accumulates anything)
+        MSM_HIP_CHECK(hipMemcpyAsync(h->snap.p, h->slabs_sym, h->sym_slab_bytes(), hipMemcpyDeviceToDevice, stream()));
+        a.snapshot = true;
+    }
+    return MSM_OK;
+}
+
+// A trajectory split over ranks: the RIGHT frames of the owned pairs, rows [own_begin + lag, min(own_end, len - lag) + lag),
+// are not the owned rows the column-sum pass summed -- one more pass over exactly those rows (into the temporary partials,
+// which the merge has just zeroed; they are zeroed again afterwards)
+int right_frames_pass(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaGeom& g = h->g;
+    std::vector<TicaChunk> tab;
+    for (long long s = 0; s < a.L.n_seq; ++s) {
+        const SegInfo t = a.L.seg(s);
+        if (!a.L.valid(t, g.lag)) continue;
+        add_chunks(tab, a.base(s, t), a.last(s, t), t.ob + g.lag, std::min<long long>(t.oe, t.len - g.lag) + g.lag, a.pl.kc, EVERY_ROW);
+    }
+    if (tab.empty()) return MSM_OK;
+    int rc = h->table2.upload(tab, 0, a.pl.total);
+    if (rc) return rc;
+    TicaArgs Q = a.P;
+    Q.chunks = h->table2.chunks();
+    Q.nchunks = h->table2.n;
+    Q.flag = h->flag + 1;  // these rows were (or will be) checked by the launch that owns them
+    if ((rc = launch_colsum(a.L.dtype_bytes, Q))) return rc;
+    hipLaunchKernelGGL(tica_shift_kernel, dim3((unsigned)ceil_div(g.F, 64)), dim3(512), 0, stream(), h->coltmp, h->shsum, h->shift,
+                       g.F, 0.0, 0, a.pl.pairsem ? (SH_B_a | SH_W_a) : SH_B_a);
+    MSM_HIP_CHECK(hipGetLastError());
+    MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, h->colbytes(), stream()));
+    return MSM_OK;
+}
+
+// what the fused and the ring multiply kernels' arguments share, once `nsteps` is set.  The merge interval in K-steps: fp32
+// partials of bf16 inputs (8 significant bits) can run 8x longer than the fp32 kernels' before the merge costs accuracy that
+// matters (stated tolerance of the mode: 1e-3)
+template <typename A>
+void img_multiply_args(A& args, const Acc& a, bool x2)
+{
+    const TicaGeom& g = a.h->g;
+    args.T = g.T;
+    args.T2 = g.T2;
+    args.ntiles_sym = g.ntiles_sym;
+    args.ntile2 = g.ntile2;
+    args.S = g.S_img;
+    args.main_steps = img_main_steps(args.nsteps, g.img_grid, g.ntile2);
+    args.kflush_steps = std::max(1, x2 ? a.P.kflush / 16 : 8 * a.P.kflush / 32);
+    args.slabs = a.h->slabs_sym;
+}
+
+// ONE launch over every K-step of the call: step records from the chunk table, then the fused kernel
+int launch_img_fused(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaGeom& g = h->g;
+    const bool x2 = a.pl.flavour & TICA_FL_X2;
+    const long long nsteps = x2 ? a.img_groups / 2 : a.img_groups / 4;
+    int rc = h->imgsteps.reserve((size_t)nsteps * sizeof(ImgStep));
+    if (rc) return rc;
+    if (h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));
+    hipLaunchKernelGGL(tica_img_steps_kernel, dim3((unsigned)a.P.nchunks), dim3(64), 0, stream(), a.P.chunks, (long long)a.L.ld * 2, g.lag,
+                       x2 ? 1 : 0, h->imgsteps.as<ImgStep>());
+    MSM_HIP_CHECK(hipGetLastError());
+    ImgFusedArgs FA;
+    memset(&FA, 0, sizeof(FA));
+    FA.steps = h->imgsteps.as<ImgStep>();
+    FA.shift = a.P.shift;
+    FA.row_bytes = (long long)a.L.ld * 2;
+    FA.lag_bytes = (long long)g.lag * (long long)a.L.ld * 2;
+    FA.nsteps = (int)nsteps;
+    img_multiply_args(FA, a, x2);
+    if (x2)
+        hipLaunchKernelGGL((tica_img_fused_kernel<true>), dim3((unsigned)g.img_grid), dim3(IMG_NT), IMG_FUSED_LDS, stream(), FA);
+    else
+        hipLaunchKernelGGL((tica_img_fused_kernel<false>), dim3((unsigned)g.img_grid), dim3(IMG_NT), IMG_FUSED_LDS, stream(), FA);
+    h->last_fused = 1;
+    return MSM_OK;
+}
+
+struct SuperChunk {
+    size_t c0, c1;      // chunks [c0, c1) of the table
+    long long g0, g1;   // ... which are groups [g0, g1) of the image
+};
+
+// Cuts the chunk table (its g0 values; img_groups closes the last chunk) into super-chunks of whole chunks, as many as a
+// ring slot holds: the ring of `ring_bytes` holds `nimg` images of Fp columns, whole (turns) or in halves (carried pack).
+// Carried: the first one short (its pre-pass is the only one the matrix pipes wait for; rho = share of multiply steps that
+// carry) but long enough to carry the second, and at most an eighth of the launch each so that short launches overlap as
+// well.  `*carry` comes in as "the carried pack can run" and goes out as "it does".  False: the ring cannot hold one chunk.
+bool plan_super_chunks(const std::vector<TicaChunk>& tab, long long img_groups, size_t ring_bytes, int Fp, int nimg, long long kc,
+                       double rho, bool* carry, long long* slot_groups_out, std::vector<SuperChunk>* scs)
+{
+    const size_t gbytes = (size_t)Fp * 16;   // one 8-pair group of ONE image
+    const long long max_chunk_groups = ceil_div(kc, 32) * 4;
+    long long slot_groups = (long long)((*carry ? ring_bytes / 2 : ring_bytes) / (gbytes * nimg));
+    slot_groups -= slot_groups % 4;
+    if (*carry && (slot_groups < 2 * max_chunk_groups || img_groups <= 2 * max_chunk_groups)) {   // (nothing to take turns with)
+        *carry = false;
+        slot_groups = (long long)(ring_bytes / (gbytes * nimg));
+        slot_groups -= slot_groups % 4;
+    }
+    if (slot_groups < max_chunk_groups) return false;
+    long long cap = slot_groups;
+    if (*carry) {
+        long long want = ceil_div(ceil_div(img_groups, 8), 4) * 4;
+        want = std::max<long long>(want, 4 * max_chunk_groups);
+        cap = std::min(cap, want);
+    }
+    const long long first_cap = *carry ? std::max<long long>(max_chunk_groups, (long long)(cap * std::max(0.25, std::min(1.0, 1.15 * rho)))) : cap;
+    for (size_t c0 = 0; c0 < tab.size() && img_groups > 0;) {
+        const long long lim = (*carry && scs->empty()) ? first_cap : cap;
+        SuperChunk sc;
+        sc.c0 = c0;
+        sc.g0 = tab[c0].g0;
+        sc.c1 = c0;
+        sc.g1 = sc.g0;
+        while (sc.c1 < tab.size()) {
+            const long long ge = sc.c1 + 1 < tab.size() ? tab[sc.c1 + 1].g0 : img_groups;
+            if (ge - sc.g0 > lim && sc.c1 > c0) break;
+            if (ge - sc.g0 > slot_groups) break;
+            sc.g1 = ge;
+            ++sc.c1;
+        }
+        scs->push_back(sc);
+        c0 = sc.c1;
+    }
+    if (scs->size() < 2) *carry = false;
+    *slot_groups_out = slot_groups;
+    return true;
+}
+
+// the images of one ring half: [u_hi | d_hi | u_mid | d_mid], `one` bytes each (the mid images in bf16x2 only)
+template <typename A>
+void ring_images(A& args, char* half, size_t one, bool x2)
+{
+    args.u_hi = reinterpret_cast<bf16x8*>(half);
+    args.d_hi = reinterpret_cast<bf16x8*>(half + one);
+    args.u_mid = x2 ? reinterpret_cast<bf16x8*>(half + 2 * one) : nullptr;
+    args.d_mid = x2 ? reinterpret_cast<bf16x8*>(half + 3 * one) : nullptr;
+}
+
+// The image is produced and consumed in SUPER-CHUNKS through a ring that the library owns (runtime.hip, img_ring):
+// tica_img_kernel packs as many chunks as the ring holds, tica_img_pp_kernel multiplies them, and so on, all on stream().
+// (Packing super-chunk k + 1 WHILE super-chunk k is multiplied on other CUs was built and measured and is slower than
+// taking turns: the packing pass needs the whole chip's memory pipelines, 40 - 64 CUs deliver 1.0 - 1.6 TB/s)
+int launch_img_ring(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaGeom& g = h->g;
+    const TicaArgs& P = a.P;
+    const int dtype_bytes = a.L.dtype_bytes;
+    const long long ld = a.L.ld;
+    const bool x2 = a.pl.flavour & TICA_FL_X2, fold = a.pl.fold;
+    const int Fp = g.T2 * 256;
+    ImgRing* ring = img_ring();
+    if (!ring) return MSM_ERR_HIP;
+    // The CARRIED pack (tica_img_dev.h): the multiply of super-chunk k packs super-chunk k + 1 into the other half of the
+    // ring in its load role; only the first (short) super-chunk takes the pre-pass kernel.  Whole 256-feature panels of
+    // 16-byte aligned rows, launches of more than one super-chunk, and few enough items per multiply step: a workgroup starts
+    // a quad of items in one multiply step and converts it in the next, so rho = (quads per pack step) / (units x multiply
+    // steps per pack step) is the share of its steps that carry when two consecutive super-chunks are equally long -- beyond
+    // ~0.9 the drain loop would do the packing with the matrix pipes idle (float32 rows of 256 features in mode bf16).
+    // Default from 1,024 features (bf16x2: 512), where it wins with the folded column sums (scripts/carryabl.py,
+    // profiles/r06_carry.txt: fit of 1M x 2048 bfloat16 rows 11.1 -> 10.5 ms, bf16x2 32.8 -> 28.8 ms; 768 features 7.15 ->
+    // 7.31 ms: the items' fp64 column sums cost what the overlap saves; bf16x2 has three times the multiply to hide behind --
+    // 768 features 18.3 -> 16.0 ms, 512 15.4 -> 13.7 ms).  MSM_TICA_IMG_CARRY=0 restores pack / multiply turns, =1 forces it
+    // at any width it can run, =2 (A/B switch of the tests): the carried pack's super-chunks and ring halves, every one
+    // packed by the pre-pass kernel.
+    const char* ce = getenv("MSM_TICA_IMG_CARRY");
+    const int cmode = ce ? atoi(ce) : -1;
+    const bool prepass_all = cmode == 2;
+    const int cy_nb = Fp / (dtype_bytes == 2 ? 64 : 32);
+    const double rho = 1.0 * cy_nb / (4.0 * g.ntile2 * (x2 ? 2 : 1));
+    bool carry = g.F % 256 == 0 && (ld * dtype_bytes) % 16 == 0 && g.ntile2 <= g.img_grid && a.L.ptr16 && cmode != 0 &&
+                 (ce || g.F >= (x2 ? 512 : 1024)) && rho <= 0.9;
+    long long slot_groups = 0;
+    std::vector<SuperChunk> scs;
+    if (!plan_super_chunks(a.img_tab, a.img_groups, ring->bytes, Fp, x2 ? 4 : 2, a.pl.kc, rho, &carry, &slot_groups, &scs))
+        return fail(MSM_ERR_INVALID, "bf16 image ring too small for %d features (MSM_TICA_IMG_RING_MB)", g.F);
+    const size_t one = (size_t)slot_groups * Fp * 16;   // bytes of one image inside the ring (half)
+    h->last_super = (long long)scs.size();
+    if (h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));
+    if (carry) {
+        // the launch's 32-pair step records (the table the fused kernel uses, with this launch's row size)
+        int rc = h->imgsteps.reserve((size_t)(a.img_groups / 4) * sizeof(ImgStep));
+        if (rc) return rc;
+        hipLaunchKernelGGL(tica_img_steps_kernel, dim3((unsigned)P.nchunks), dim3(64), 0, stream(), P.chunks, ld * dtype_bytes, g.lag, 0,
+                           h->imgsteps.as<ImgStep>());
+        MSM_HIP_CHECK(hipGetLastError());
+        if (fold) {
+            long long np_max = 0;
+            for (const SuperChunk& sc : scs) np_max = std::max(np_max, (sc.g1 - sc.g0) / 4);
+            if ((rc = h->colsteps.reserve((size_t)np_max * Fp * sizeof(double)))) return rc;
+        }
+    }
+    for (size_t k = 0; k < scs.size(); ++k) {
+        const SuperChunk& sc = scs[k];
+        char* const half = ring->p + ((carry && (k & 1)) ? ring->bytes / 2 : 0);
+        if (!carry || k == 0 || prepass_all) {
+            ImgArgs IA;
+            memset(&IA, 0, sizeof(IA));
+            IA.chunks = P.chunks + sc.c0;
+            IA.nchunks = (long long)(sc.c1 - sc.c0);
+            IA.ld = ld;
+            IA.F = g.F;
+            IA.Fp = Fp;
+            IA.lag = g.lag;
+            IA.dtype_bytes = dtype_bytes;
+            IA.shift = P.shift;
+            IA.colA = fold ? h->foldimg.as<double>() + sc.c0 * (size_t)g.F : nullptr;
+            IA.g_off = sc.g0;
+            ring_images(IA, half, one, x2);
+            const dim3 g1((unsigned)(sc.c1 - sc.c0), (unsigned)g.T2);
+            if (x2)
+                hipLaunchKernelGGL(tica_img_kernel<true>, g1, dim3(256), 0, stream(), IA);
+            else
+                hipLaunchKernelGGL(tica_img_kernel<false>, g1, dim3(256), 0, stream(), IA);
+            MSM_HIP_CHECK(hipGetLastError());
+        }
+        ImgMfmaArgs MA;
+        memset(&MA, 0, sizeof(MA));
+        ring_images(MA, half, one, x2);
+        MA.nsteps = x2 ? (sc.g1 - sc.g0) / 2 : (sc.g1 - sc.g0) / 4;
+        MA.Fp = Fp;
+        img_multiply_args(MA, a, x2);
+        const bool carries = carry && !prepass_all && k + 1 < scs.size();
+        if (carries) {
+            const SuperChunk& nx = scs[k + 1];
+            MA.cy.psteps = h->imgsteps.as<ImgStep>() + nx.g0 / 4;
+            MA.cy.shift = P.shift;
+            ring_images(MA.cy, ring->p + ((k & 1) ? 0 : ring->bytes / 2), one, x2);
+            MA.cy.colS = fold ? h->colsteps.as<double>() : nullptr;
+            MA.cy.row_bytes = ld * dtype_bytes;
+            MA.cy.lag_bytes = (long long)g.lag * ld * dtype_bytes;
+            MA.cy.np = (int)((nx.g1 - nx.g0) / 4);
+            MA.cy.nb = cy_nb;
+            // a workgroup's multiply steps / its quads (every workgroup multiplies ~ nsteps x units / grid steps)
+            const long long wsteps = MA.nsteps * g.ntile2 / g.img_grid;
+            const long long wquads = ceil_div(ceil_div((long long)MA.cy.np * cy_nb, 4), g.img_grid);
+            MA.cy.stride = (int)std::max<long long>(1, wsteps / std::max<long long>(1, wquads));
+            {
+                const char* ae = getenv("MSM_TICA_IMG_CARRY_ABL");   // timing ablations only (tica_img_dev.h, img_carry_phase)
+                MA.cy.pad = ae ? atoi(ae) : 0;
+            }
+            h->last_carried = 1;
+        }
+#define MSM_IMG_PP_LAUNCH(X2_, CY_) \
+        hipLaunchKernelGGL((tica_img_pp_kernel<X2_, IMG_LAG, false, 0, CY_>), dim3((unsigned)g.img_grid), dim3(IMG_NT), (CY_) ? IMG_PP_CARRY_LDS : IMG_PP_LDS, stream(), MA)
+        if (!carries) {
+            if (x2) MSM_IMG_PP_LAUNCH(true, 0);
+            else MSM_IMG_PP_LAUNCH(false, 0);
+        } else if (dtype_bytes == 2) {
+            if (x2) MSM_IMG_PP_LAUNCH(true, 2);
+            else MSM_IMG_PP_LAUNCH(false, 2);
+        } else {
+            if (x2) MSM_IMG_PP_LAUNCH(true, 4);
+            else MSM_IMG_PP_LAUNCH(false, 4);
+        }
+#undef MSM_IMG_PP_LAUNCH
+        MSM_HIP_CHECK(hipGetLastError());
+        if (carries && fold) {
+            const SuperChunk& nx = scs[k + 1];
+            hipLaunchKernelGGL(tica_img_colsum_steps_kernel, dim3((unsigned)(nx.c1 - nx.c0), (unsigned)ceil_div(g.F, 256)), dim3(256), 0, stream(),
+                               P.chunks + nx.c0, (long long)(nx.c1 - nx.c0), nx.g0, nx.g1, h->colsteps.as<double>(), g.F, Fp,
+                               h->foldimg.as<double>() + nx.c0 * (size_t)g.F);
+            MSM_HIP_CHECK(hipGetLastError());
+        }
+    }
+    return MSM_OK;
+}
+
+// whole-matrix sum/difference kernel, float or double rows: the handle's variant, or the element-wise SymwA for rows too
+// short for a 16-byte piece
+int launch_symw(Acc& a)
+{
+    msm_tica* h = a.h;
+    SymwArgs WA;
+    WA.T = a.P;
+    WA.slabs = h->slabs_w;
+    const dim3 grid(a.pl.G);
+    const bool f64 = a.pl.path == TICA_SYMW64;
+    if (!(a.pl.flavour & TICA_FL_VEC)) {
+        if (f64) hipLaunchKernelGGL((tica_symw_f64_kernel<SymwA, false>), grid, dim3(SymwA::NTH), SymwA::LDS64, stream(), WA);
+        else hipLaunchKernelGGL((tica_symw_f32_kernel<SymwA, false>), grid, dim3(SymwA::NTH), SymwA::LDS, stream(), WA);
+    } else {
+        symw_visit(h->g.symw_var, [&](auto cfg) {
+            using Cfg = decltype(cfg);
+            if (!f64) hipLaunchKernelGGL((tica_symw_f32_kernel<Cfg, true>), grid, dim3(Cfg::NTH), Cfg::LDS, stream(), WA);
+            else if constexpr (symw_has64<Cfg>) hipLaunchKernelGGL((tica_symw_f64_kernel<Cfg, true>), grid, dim3(Cfg::NTH), Cfg::LDS64, stream(), WA);
+        });
+    }
+    h->symw_used = std::max(h->symw_used, (int)std::min<long long>(a.pl.G, a.P.nchunks));
+    return MSM_OK;
+}
+
+int launch_sym(Acc& a)
+{
+    const dim3 grid(a.pl.G);
+    const TicaArgs& P = a.P;
+    switch (a.pl.flavour) {
+#define MSM_SYM_LAUNCH(...) hipLaunchKernelGGL((tica_sym_f32_kernel<__VA_ARGS__>), grid, dim3(NT), LDSSYM, stream(), P); break
+        case TICA_FL_FOLD | TICA_FL_REM: MSM_SYM_LAUNCH(false, true, true);
+        case TICA_FL_REM: MSM_SYM_LAUNCH(false, false, true);
+        case TICA_FL_EDGE | TICA_FL_REM: MSM_SYM_LAUNCH(true, false, true);
+        case TICA_FL_FOLD: MSM_SYM_LAUNCH(false, true);
+        case 0: MSM_SYM_LAUNCH(false, false);
+        default: MSM_SYM_LAUNCH(true, false);
+#undef MSM_SYM_LAUNCH
+    }
+    return MSM_OK;
+}
+
+int launch_cg32(Acc& a)
+{
+    const dim3 grid(a.pl.G);
+    const TicaArgs& P = a.P;
+    if (a.pl.flavour == TICA_FL_ALIGNED)
+        hipLaunchKernelGGL((tica_mfma_f32_kernel<true, false>), grid, dim3(NT), LDS32, stream(), P);
+    else if (a.pl.flavour & TICA_FL_ALIGNED)
+        hipLaunchKernelGGL((tica_mfma_f32_kernel<true, true>), grid, dim3(NT), LDS32, stream(), P);
+    else
+        hipLaunchKernelGGL((tica_mfma_f32_kernel<false, true>), grid, dim3(NT), LDS32, stream(), P);
+    return MSM_OK;
+}
+
+int launch_cg64(Acc& a)
+{
+    if (a.L.dtype_bytes == 4)
+        hipLaunchKernelGGL(tica_mfma_f64_kernel<float>, dim3(a.pl.G), dim3(NT), LDS64, stream(), a.P);
+    else
+        hipLaunchKernelGGL(tica_mfma_f64_kernel<double>, dim3(a.pl.G), dim3(NT), LDS64, stream(), a.P);
+    return MSM_OK;
+}
+
+// 3') folded column sums: temporary partials -> [left sums | right sums] per slot, finite check of the folded sums (a
+//     rejected launch is undone: the slabs as they were, nothing of it in the column sums or the shift), shift and merge
+int fold_fixup(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaGeom& g = h->g;
+    const dim3 grid((unsigned)ceil_div((size_t)NCB * g.F, 256));
+    if (a.pl.img())
+        hipLaunchKernelGGL(tica_fold_fix_img_kernel, grid, dim3(256), 0, stream(), h->coltmp, h->foldimg.as<double>(), g.F, a.P.nchunks, h->flag);
+    else
+        hipLaunchKernelGGL(tica_fold_fix_kernel, grid, dim3(256), 0, stream(), h->coltmp, h->fold, g.F, g.S_sym, h->flag);
+    MSM_HIP_CHECK(hipGetLastError());
+    int rc = MSM_OK;
+    if (a.check_finite && (rc = check_finite_flag(a, true))) return rc;
+    return shift_and_merge(a, 0);
+}
+
+int env_switch(const char* name)   // an integer switch of the environment: -1 unset (or negative), else its value
+{
+    const char* e = getenv(name);
+    return e ? std::max(-1, atoi(e)) : -1;
+}
+
+// Device-resident trajectories only.  The sequencer: validate and count, plan, chunk table, column sums or boundary pass,
+// extra pass for segments, the MFMA launch of the plan's path, after_launch, folded fix-up and check, bookkeeping.
+// after_launch: host work to run once the accumulation kernel is queued and before this call's first wait for it (the
+// staged host path copies its NEXT group of trajectories there)
 int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t* n_rows,
                            msm_idx_t n_seq, int dtype_bytes, msm_idx_t ld, int check_finite,
                            msm_idx_t* n_skipped, const SegInfo* segs = nullptr, const std::function<int()>* after_launch = nullptr)
 {
-    // after_launch: host work to run once the accumulation kernel is queued and before this call's first wait for it (the
-    // staged host path copies its NEXT group of trajectories there)
-    long long total = 0, nvalid = 0, skipped = 0;
-    bool aligned = (h->F % 4 == 0) && (ld % 4 == 0);
-    auto seg_of = [&](msm_idx_t s) {
-        SegInfo g;
-        if (segs) g = segs[s];
-        else { g.len = n_rows[s]; g.off = 0; g.ob = 0; g.oe = n_rows[s]; }
-        return g;
-    };
+    const TicaGeom& g = h->g;
+    Acc a{h, ptrs, check_finite};
+    TicaLaunch& L = a.L;
+    L.dtype_bytes = dtype_bytes;
+    L.ld = ld;
+    L.n_seq = n_seq;
+    L.n_rows = n_rows;
+    L.segs = segs;
+    L.dims4 = (g.F % 4 == 0) && (ld % 4 == 0);
+    long long skipped = 0;
     for (msm_idx_t s = 0; s < n_seq; ++s) {
-        const SegInfo g = seg_of(s);
-        if (g.len > h->lag && g.oe > g.ob) {
-            total += g.oe - g.ob;
-            ++nvalid;
-            if (((uintptr_t)ptrs[s]) & 15) aligned = false;
-        } else if (g.len <= h->lag) {
+        const SegInfo t = L.seg(s);
+        if (((uintptr_t)ptrs[s]) & 15) L.ptr16_all = false;
+        if (L.valid(t, g.lag)) {
+            if (((uintptr_t)ptrs[s]) & 15) L.ptr16 = false;
+        } else if (t.len <= g.lag) {
             ++skipped;
         }
     }
     if (n_skipped) *n_skipped = skipped;
-    if (nvalid == 0) return MSM_OK;
+    L.fold_switch = env_switch("MSM_TICA_FOLD");   // read per launch (A/B switches of the tests); 0 = never, 2 = always
+    {
+        const char* fe = getenv("MSM_TICA_IMG_FUSED");   // 1 forces the fused kernel, any other value the image ring
+        L.fused_switch = fe ? (atoi(fe) == 1 ? 1 : 0) : -1;
+    }
+    const TicaPlan& pl = a.pl = tica_plan(g, L);
+    if (pl.nvalid == 0) return MSM_OK;
     h->reduced = false;
 
-    // chunk size: every cohort gets work, fp32 partials stay <= KCMAX frames
-    const bool bfmode = (h->mode == MSM_TICA_BF16 || h->mode == MSM_TICA_BF16X2);
-    const bool useimg = bfmode && h->img_on && (dtype_bytes == 4 || dtype_bytes == 2);  // packed bf16 image + 256 x 256 tiles
-    // The FUSED kernel (round 5): bfloat16-STORED rows of whole 256-feature panels skip the image -- the MFMA kernel's load role
-    // stages the raw rows in LDS and forms the packets itself (tica_img_fused_kernel; its slabs equal the packed-image
-    // pipeline's bit for bit).  Half the fabric traffic and no ring.  Round 6 (VERDICT r5 #3a): it is the DEFAULT where it is
-    // faster -- up to 512 features -- and the packed image from 768 (scripts/fusedprobe.py, profiles/r06_fused_probe.txt,
-    // fit wall time fused / image, bf16 | bf16x2: F = 256 0.80 | 0.77, 512 0.88 | 0.84, 768 1.08 | 0.98, 1024 1.09 | 1.06,
-    // 1536 1.27 | 1.00, 2048 1.35 | 1.22: a unit of H or D needs x_t AND x_{t+tau} of both panels, and from three panels per
-    // side the raw rows' three trips through the LDS cost more than the image's write and read).
-    // MSM_TICA_IMG_FUSED=0 / 1 (read per launch) forces either.
-    bool usefused = false;
-    if (useimg && dtype_bytes == 2 && h->F % 256 == 0 && ld % 8 == 0) {
-        const char* fe = getenv("MSM_TICA_IMG_FUSED");
-        usefused = fe ? atoi(fe) == 1 : h->F <= 512;
-        for (msm_idx_t s = 0; s < n_seq && usefused; ++s)
-            if (((uintptr_t)ptrs[s]) & 15) usefused = false;   // 16-byte LDS-direct row pieces
-    }
-    // (a bf16 mode whose 256-wide tiles do not fit one resident round -- beyond 3,840 features -- runs the fp32 C/G kernel:
-    //  the mode is an accuracy floor, not a promise of the bf16 pipe; bfloat16-stored rows there take the fp64 kernel)
-    const bool use32 = dtype_bytes == 4 && (h->mode == MSM_TICA_F32 || (bfmode && !useimg));
-    // F <= 256, fp32 mode: the whole-matrix sum/difference kernel (any alignment a float row can have; tica_symw_dev.h)
-    // ... and float64 rows of up to 128 features on the same slabs (tica_symw_f64_kernel: the fp64 matrix pipe)
-    const bool symw64 = dtype_bytes == 8 && h->mode == MSM_TICA_F32 && h->symw64;
-    const bool usesymw = (use32 && h->mode == MSM_TICA_F32 && h->symw) || symw64;
-    const int bk = usesymw ? h->symw_KS : (use32 || useimg) ? BK32 : BK64;
-    const bool usesym = !usesymw && ((use32 && h->mode == MSM_TICA_F32 && h->sym && h->slabs_sym && aligned) || useimg);  // sum/difference slabs (H/D kernel: 16-byte aligned rows only)
-    const bool pairsem = usesym || usesymw;   // pair semantics: a frame counts once per valid pair it is in
-    const int S = symw64 ? std::min(h->symw_S, h->symw_S64) : usesymw ? h->symw_S : useimg ? h->S_img : usesym ? h->sym_cohorts : use32 ? h->S32 : h->S64;  // one resident round
-    const bool symrem = usesym && !useimg && h->sym_grid > S * h->ntiles_sym;              // ... + a remainder cohort
-    const int G = usesymw ? S : symrem ? h->sym_grid : S * (usesym ? h->ntiles_sym : h->ntiles);
-    long long kc = ceil_div(total, S);
-    kc = ceil_div(kc, bk) * bk;
-    if (kc > KCMAX) kc = KCMAX;
-    // a chunk = one workgroup column of the packing pre-pass: finer chunks, more of them in flight (round 5, measured at 1M x 2048
-    // bfloat16-stored, pack + multiply: 2048 -> 12.7 ms, 1024 -> 12.3, 512 -> 11.9, 256 -> 11.6; 1024 keeps the per-chunk
-    // column sums of a 6.25M-frame fit at 100 MB)
-    if (useimg && kc > 1024) kc = 1024;
-    if (kc < bk) kc = bk;
-    if (usesymw) {
-        // every workgroup is a cohort of its own and a trajectory is cut into whole chunks: with about one chunk per
-        // workgroup the launch lasts as long as the workgroups that got two (2M x 171 as 200 x 10,000: 600 chunks on 512
-        // workgroups, 1.9 ms where the flops need 1.1).  Eight chunks per workgroup and more, but chunks of at least four
-        // K-steps / 256 frames (a chunk starts with an exposed load).
-        const long long kmin = std::min<long long>(KCMAX, std::max<long long>(256, 4LL * bk));
-        kc = ceil_div(ceil_div(total, 8LL * S), bk) * bk;
-        kc = std::min<long long>(KCMAX, std::max<long long>(kc, kmin));
-    }
-    if (kc == KCMAX && total < 16LL * KCMAX * S && !useimg && !usesymw) {
-        // Few chunks per cohort (one rank's share of a strong-scaled fit: 1.25M frames = 7.35 chunks of 4096 per cohort, the
-        // busiest cohort does 8): cohorts take chunks round-robin, so the launch lasts as long as the fullest one.  Try smaller
-        // chunks and keep the size whose fullest cohort -- plus ~16 frames' worth of prologue per chunk -- is lightest.
-        long long best = -1, best_kc = kc;
-        std::vector<long long> load((size_t)S);
-        for (long long cand : {4096LL, 3072LL, 2560LL, 2048LL, 1536LL, 1024LL}) {
-            std::fill(load.begin(), load.end(), 0LL);
-            long long c = 0;
-            for (msm_idx_t s = 0; s < n_seq; ++s) {
-                const SegInfo g = seg_of(s);
-                if (g.len <= h->lag || g.oe <= g.ob) continue;
-                const long long own = g.oe - g.ob, nch = ceil_div(own, cand);
-                const long long piece = ceil_div(ceil_div(own, nch), bk) * bk;
-                for (long long r0 = 0; r0 < own; r0 += piece, ++c) load[(size_t)(c % S)] += std::min(piece, own - r0) + 16;
-            }
-            const long long worst = *std::max_element(load.begin(), load.end());
-            if (best < 0 || worst < best) {
-                best = worst;
-                best_kc = cand;
-            }
-        }
-        kc = best_kc;
-    }
-
-    TicaArgs P;
+    TicaArgs& P = a.P;
     memset(&P, 0, sizeof(P));
     P.ld = ld;
-    P.kc = (int)kc;
-    P.F = h->F;
-    P.lag = h->lag;
-    P.T = h->T;
-    P.ntiles = usesym ? h->ntiles_sym : h->ntiles;
-    P.S = S;
-    P.slabs = usesym ? h->slabs_sym : h->slabs;
+    P.kc = (int)pl.kc;
+    P.F = g.F;
+    P.lag = g.lag;
+    P.T = g.T;
+    P.ntiles = pl.sym_slabs() ? g.ntiles_sym : g.ntiles;
+    P.S = pl.S;
+    P.slabs = pl.sym_slabs() ? h->slabs_sym : h->slabs;
     P.colpart = h->coltmp;
     P.flag = h->flag;
     P.dbg = h->dbg;
-    {
-        // fp32 partial sums of the SHIFTED frames are sigma^2-sized, so two chunks (8192 frames) can share a merge; raw
-        // moments (no shift) keep the 4096-frame partials of round 1
-        P.kflush = h->shift_on ? 2 * KFLUSH_SYM : KFLUSH_SYM;
-    }
-    {
-        // Cohort pacing (the workgroups of a cohort wait for each other at chunk boundaries, bounded).  C/G kernel, measured
-        // at 10M x 512: the L2 fabric-side fetch drops from 207 GB to 79-82 GB per launch but the kernel is 4 % slower
-        // (78.4 -> 81.7 ms): opt-in there.  Sum/difference kernel WITH the wave-priority window (round 2): 110 GB -> 32 GB
-        // fetched per launch (1.8x the algorithmic bytes instead of 5.5x) AND 1 % faster (50.45 -> 49.8 ms; without the
-        // priority window pacing cost 2 %): on there.
-        const bool pace = usesym && !useimg;
-        P.cosync = pace ? h->cosync : nullptr;
-    }
+    P.kflush = pl.kflush;
+    P.cosync = pl.pace ? h->cosync : nullptr;
+    if (!segs) a.key = table_key(a);
+    int rc = main_table(a);
+    if (rc) return rc;
+    P.n_main = pl.n_main(P.nchunks);
+    h->last_plan = pl;
+    h->last_nchunks = P.nchunks;
+    h->last_super = 0;
 
-    // what the chunk tables are a function of (FNV-1a over the pointer / length tables and the launch's parameters; 0 = no key)
-    unsigned long long table_key = 0;
-    if (!segs) {
-        unsigned long long hsh = 1469598103934665603ULL;
-        auto mix = [&](unsigned long long v) {
-            for (int b = 0; b < 8; ++b) {
-                hsh ^= (v >> (8 * b)) & 0xffULL;
-                hsh *= 1099511628211ULL;
-            }
-        };
-        mix((unsigned long long)n_seq);
-        mix((unsigned long long)dtype_bytes);
-        mix((unsigned long long)ld);
-        mix((unsigned long long)kc);
-        mix((unsigned long long)h->lag);
-        mix((unsigned long long)bk);
-        mix(useimg ? 1ULL : 0ULL);
-        for (msm_idx_t s = 0; s < n_seq; ++s) {
-            mix((unsigned long long)(uintptr_t)ptrs[s]);
-            mix((unsigned long long)n_rows[s]);
-        }
-        table_key = hsh ? hsh : 1ULL;
-    }
-    long long img_groups = 0;  // bf16 image path: 8-pair groups of the packed image (whole K-steps per chunk)
-    std::vector<TicaChunk> img_tab;   // ... and its chunk table (the super-chunk loop below cuts it into ring slots)
-    if (nvalid == 1 && n_seq == 1 && !segs && !useimg) {
-        P.chunks = nullptr;
-        P.single.base = ptrs[0];
-        P.single.row0 = 0;
-        P.single.len = n_rows[0];
-        P.single.last = n_rows[0] - 1;
-        P.single.n = 0;
-        P.nchunks = ceil_div(n_rows[0], kc);
-    } else if (!segs && table_key != 0 && h->table_key == table_key && h->table_total == total) {
-        P.chunks = h->table.as<TicaChunk>();     // the same trajectories as the last launch: its table is still on the device
-        P.nchunks = h->table_n;
-        img_groups = h->table_img_groups;
-        if (useimg) img_tab = h->table_host;
-    } else {
-        std::vector<TicaChunk> tab;
-        tab.reserve((size_t)(total / kc + nvalid + 1));
-        for (msm_idx_t s = 0; s < n_seq; ++s) {
-            const SegInfo g = seg_of(s);
-            if (g.len <= h->lag || g.oe <= g.ob) continue;
-            const long long own = g.oe - g.ob;
-            const long long nch = ceil_div(own, kc);
-            long long piece = ceil_div(ceil_div(own, nch), bk) * bk;
-            for (long long r0 = g.ob; r0 < g.oe; r0 += piece) {
-                TicaChunk ch;
-                // virtual row 0 of the trajectory (never dereferenced outside the slice: rows are
-                // clamped to [row0, last])
-                ch.base = (const char*)ptrs[s] - (ptrdiff_t)g.off * (ptrdiff_t)ld * dtype_bytes;
-                ch.row0 = r0;
-                ch.len = g.len;
-                ch.n = (int)((g.oe - r0) < piece ? (g.oe - r0) : piece);
-                ch.pad = 0;
-                ch.last = g.off + n_rows[s] - 1;
-                ch.g0 = img_groups;
-                if (useimg) {
-                    long long nv = std::min<long long>(ch.n, g.len - h->lag - r0);
-                    if (nv < 0) nv = 0;
-                    img_groups += ceil_div(nv, 32) * 4;
-                }
-                tab.push_back(ch);
-            }
-        }
-        int rc = h->table.reserve(tab.size() * sizeof(TicaChunk));
-        if (rc) return rc;
-        MSM_HIP_CHECK(hipMemcpyAsync(h->table.p, tab.data(), tab.size() * sizeof(TicaChunk),
-                                     hipMemcpyHostToDevice, stream()));
-        MSM_HIP_CHECK(hipStreamSynchronize(stream()));  // `tab` is pageable host memory
-        P.chunks = h->table.as<TicaChunk>();
-        P.nchunks = (long long)tab.size();
-        h->table_key = segs ? 0 : table_key;
-        h->table_total = total;
-        h->table_n = P.nchunks;
-        h->table_img_groups = img_groups;
-        if (useimg) {
-            if (!segs) h->table_host = tab;
-            img_tab.swap(tab);
-        }
-    }
-
-    P.n_main = P.nchunks;
-    if (symrem) {
-        // chunks of the remainder cohort: its R workgroups walk them once per round, the whole cohorts share the others
-        // S ways -- equal time when n_rem x rounds = n_main / S
-        const int R = G - S * h->ntiles_sym, rounds = (int)ceil_div(h->ntiles_sym, R);
-        const long long n_rem = (P.nchunks + ((long long)S * rounds + 1) / 2) / ((long long)S * rounds + 1);
-        P.n_main = P.nchunks - n_rem;
-    }
-
-    // Folded column sums (sum/difference kernel, whole trajectories of >= 2 lag frames, full tiles, launches big enough
-    // for a pass over X to matter): no column-sum pass over X ahead of the MFMA kernel -- the kernel's staging lanes sum the
-    // left frames, a column-sum pass over the first and last `lag` rows of every trajectory supplies what separates the
-    // right frames' sums from the left frames' (and checks those rows), and the finite check is made on the sums afterwards.
-    bool fold = false;
-    if (usesym && !segs && h->fold && !usefused && (useimg || h->F % TM == 0)) {   // (bf16 image path: the pre-pass sums while it packs; the fused kernel has no pre-pass: column-sum pass)
-        // MSM_TICA_FOLD, read per launch (A/B switch of the tests): 0 = never, 2 = whatever the size; default: launches of
-        // at least 2^26 elements (frames x features)
-        const char* fe = getenv("MSM_TICA_FOLD");
-        const int fmode = fe ? atoi(fe) : 1;
-        fold = fmode != 0 && (fmode == 2 || (double)total * h->F >= 67108864.0);
-        for (msm_idx_t s = 0; s < n_seq && fold; ++s)
-            if (n_rows[s] > h->lag && n_rows[s] < 2 * (long long)h->lag) fold = false;
-        if (2 * (long long)h->lag * nvalid > total / 4) fold = false;   // the boundary rows would be a pass of their own
-    }
-    const bool shifted = h->shift_on && (use32 || useimg || symw64);
-    // 1b) mean shift bookkeeping (fp32 / bf16 kernels): the raw column sums of what this launch accumulates under the
-    //     shift, and -- first shifted launch of the handle, `set_r` -- the reference row r = this launch's column means
-    auto shift_and_merge = [&](int set_r) -> int {
-        if (shifted) {
-            long long n_call = 0, nw_call = 0, nmean = 0;
-            for (msm_idx_t s = 0; s < n_seq; ++s) {
-                const SegInfo g = seg_of(s);
-                if (g.len <= h->lag || g.oe <= g.ob) continue;
-                const long long n0 = std::max<long long>(0, std::min<long long>(g.oe, g.len - h->lag) - g.ob);
-                const long long nt = std::max<long long>(0, g.oe - std::max<long long>(g.ob, h->lag));
-                n_call += n0;
-                nmean += n0 + nt;
-                nw_call += (segs && !pairsem) ? n0 + nt : 2 * n0;
-            }
-            const int what = !segs ? (SH_A_a | SH_B_b | SH_W_ab) : pairsem ? (SH_A_a | SH_W_a) : (SH_A_a | SH_W_ab);
-            hipLaunchKernelGGL(tica_shift_kernel, dim3((unsigned)ceil_div(h->F, 64)), dim3(512), 0, stream(), h->coltmp,
-                               h->shsum, h->shift, h->F, 1.0 / (double)std::max<long long>(1, nmean), set_r, what);
-            MSM_HIP_CHECK(hipGetLastError());
-            h->have_shift = true;
-            h->n_sh += n_call;
-            h->nw_sh += nw_call;
-        }
-        const size_t n = (size_t)NCB * 2 * h->F;
-        hipLaunchKernelGGL(tica_colmerge_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream(),
-                           h->colpart, h->coltmp, n);
-        MSM_HIP_CHECK(hipGetLastError());
-        return MSM_OK;
-    };
-    bool snapshot = false;
-    const size_t slab_bytes = usesym && h->slabs_sym ? (size_t)h->S_sym * h->ntiles_sym * 2 * TM * TM * sizeof(double) : 0;
-    if (!fold) {
-        // 1) column sums + finite check into the temporary partials
-        if (dtype_bytes == 4)
-            hipLaunchKernelGGL(tica_colsum_kernel<float>, dim3(NCB), dim3(NT), 0, stream(), P);
-        else if (dtype_bytes == 2)
-            hipLaunchKernelGGL(tica_colsum_kernel<__bf16>, dim3(NCB), dim3(NT), 0, stream(), P);
-        else
-            hipLaunchKernelGGL(tica_colsum_kernel<double>, dim3(NCB), dim3(NT), 0, stream(), P);
-        MSM_HIP_CHECK(hipGetLastError());
-        if (check_finite) {
-            int f[2] = {0, 0};
-            MSM_HIP_CHECK(hipMemcpyAsync(f, h->flag, sizeof(f), hipMemcpyDeviceToHost, stream()));
-            MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-            if (f[0]) {
-                MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, (size_t)NCB * 2 * h->F * sizeof(double), stream()));
-                MSM_HIP_CHECK(hipMemsetAsync(h->flag, 0, sizeof(int), stream()));
-                return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
-            }
-        }
-        if (shifted) P.shift = h->shift;
-        int rc = shift_and_merge(h->have_shift ? 0 : 1);
-        if (rc) return rc;
-    } else {
-        // 1') the boundary rows: [0, lag) count as left frames only (chunk length "infinite"), [len - lag, len) as right
-        //     frames only, so the temporary partials receive a = sum of the first rows | b = sum of the last rows
-        std::vector<TicaChunk> tab;
-        const bool have2 = table_key != 0 && h->table2_key == table_key && h->table2_total == total;   // (the boundary table of the same trajectories: still there)
-        for (msm_idx_t s = 0; s < n_seq && !have2; ++s) {
-            const long long len = n_rows[s];
-            if (len <= h->lag) continue;
-            for (int side = 0; side < 2; ++side) {
-                const long long b0 = side ? len - h->lag : 0, b1 = b0 + h->lag;
-                for (long long r0 = b0; r0 < b1; r0 += kc) {
-                    TicaChunk ch;
-                    ch.base = ptrs[s];
-                    ch.row0 = r0;
-                    ch.len = side ? len : (long long)1 << 60;
-                    ch.n = (int)std::min<long long>(kc, b1 - r0);
-                    ch.pad = 0;
-                    ch.last = len - 1;
-                    ch.g0 = 0;
-                    tab.push_back(ch);
-                }
-            }
-        }
-        int rc = MSM_OK;
-        if (!have2) {
-            if ((rc = h->table2.reserve(tab.size() * sizeof(TicaChunk)))) return rc;
-            MSM_HIP_CHECK(hipMemcpyAsync(h->table2.p, tab.data(), tab.size() * sizeof(TicaChunk), hipMemcpyHostToDevice, stream()));
-            MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-            h->table2_key = table_key;
-            h->table2_total = total;
-            h->table2_n = (long long)tab.size();
-        }
-        TicaArgs Q = P;
-        Q.chunks = h->table2.as<TicaChunk>();
-        Q.nchunks = h->table2_n;
-        if (dtype_bytes == 4)
-            hipLaunchKernelGGL(tica_colsum_kernel<float>, dim3(NCB), dim3(NT), 0, stream(), Q);
-        else
-            hipLaunchKernelGGL(tica_colsum_kernel<__bf16>, dim3(NCB), dim3(NT), 0, stream(), Q);
-        MSM_HIP_CHECK(hipGetLastError());
-        if (shifted) {
-            if (!h->have_shift) {
-                double* sp = h->fold + (size_t)h->S_sym * h->F;
-                if (dtype_bytes == 4)
-                    hipLaunchKernelGGL(tica_fold_sample_kernel<float>, dim3((unsigned)ceil_div(h->F, 64), FOLD_NB), dim3(256), 0, stream(), P, sp);
-                else
-                    hipLaunchKernelGGL(tica_fold_sample_kernel<__bf16>, dim3((unsigned)ceil_div(h->F, 64), FOLD_NB), dim3(256), 0, stream(), P, sp);
-                hipLaunchKernelGGL(tica_fold_setr_kernel, dim3((unsigned)ceil_div(h->F, 256)), dim3(256), 0, stream(), sp, h->shift, h->F);
-                MSM_HIP_CHECK(hipGetLastError());
-            }
-            P.shift = h->shift;
-        }
-        if (useimg) {
-            if ((rc = h->foldimg.reserve((size_t)P.nchunks * h->F * sizeof(double)))) return rc;   // every word is written by the pre-pass
-        } else {
-            P.colA = h->fold;
-            P.zrow = reinterpret_cast<const float*>(h->fold + (size_t)(h->S_sym + FOLD_NB) * h->F);   // zeroed at creation, never written
-            MSM_HIP_CHECK(hipMemsetAsync(h->fold, 0, (size_t)h->S_sym * h->F * sizeof(double), stream()));
-        }
-        if (check_finite && h->slabs_dirty) {   // a rejected launch leaves the state untouched (utils/validation.py:68-74 raises
-            if ((rc = h->snap.reserve(slab_bytes))) return rc;   // before tica.py:401 accumulates anything)
-            MSM_HIP_CHECK(hipMemcpyAsync(h->snap.p, h->slabs_sym, slab_bytes, hipMemcpyDeviceToDevice, stream()));
-            snapshot = true;
-        }
-    }
-    if (shifted && segs) {
-        // a trajectory split over ranks: the RIGHT frames of the owned pairs, rows [own_begin + lag, min(own_end, len - lag)
-        // + lag), are not the owned rows the pass above summed -- one more column-sum pass over exactly those rows (into
-        // the temporary partials, which the merge above has just zeroed; they are zeroed again afterwards)
-        std::vector<TicaChunk> tab;
-        for (msm_idx_t s = 0; s < n_seq; ++s) {
-            const SegInfo g = seg_of(s);
-            if (g.len <= h->lag || g.oe <= g.ob) continue;
-            const long long b0 = g.ob + h->lag, b1 = std::min<long long>(g.oe, g.len - h->lag) + h->lag;
-            for (long long r0 = b0; r0 < b1; r0 += kc) {
-                TicaChunk ch;
-                ch.base = (const char*)ptrs[s] - (ptrdiff_t)g.off * (ptrdiff_t)ld * dtype_bytes;
-                ch.row0 = r0;
-                ch.len = (long long)1 << 60;  // every row counts (as "s0")
-                ch.n = (int)std::min<long long>(kc, b1 - r0);
-                ch.pad = 0;
-                ch.last = g.off + n_rows[s] - 1;
-                tab.push_back(ch);
-            }
-        }
-        if (!tab.empty()) {
-            h->table2_key = 0;
-            int rc = h->table2.reserve(tab.size() * sizeof(TicaChunk));
-            if (rc) return rc;
-            MSM_HIP_CHECK(hipMemcpyAsync(h->table2.p, tab.data(), tab.size() * sizeof(TicaChunk), hipMemcpyHostToDevice, stream()));
-            MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-            TicaArgs Q = P;
-            Q.chunks = h->table2.as<TicaChunk>();
-            Q.nchunks = (long long)tab.size();
-            Q.flag = h->flag + 1;  // these rows were (or will be) checked by the launch that owns them
-            if (dtype_bytes == 4)
-                hipLaunchKernelGGL(tica_colsum_kernel<float>, dim3(NCB), dim3(NT), 0, stream(), Q);
-            else if (dtype_bytes == 2)
-                hipLaunchKernelGGL(tica_colsum_kernel<__bf16>, dim3(NCB), dim3(NT), 0, stream(), Q);
-            else
-                hipLaunchKernelGGL(tica_colsum_kernel<double>, dim3(NCB), dim3(NT), 0, stream(), Q);
-            hipLaunchKernelGGL(tica_shift_kernel, dim3((unsigned)ceil_div(h->F, 64)), dim3(512), 0, stream(), h->coltmp,
-                               h->shsum, h->shift, h->F, 0.0, 0, pairsem ? (SH_B_a | SH_W_a) : SH_B_a);
-            MSM_HIP_CHECK(hipGetLastError());
-            MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, (size_t)NCB * 2 * h->F * sizeof(double), stream()));
-        }
-    }
+    if ((rc = pl.fold ? boundary_pass(a) : colsum_pass(a))) return rc;
+    if (pl.shifted && segs && (rc = right_frames_pass(a))) return rc;
     // 2) the MFMA pass
-    MSM_HIP_CHECK(hipMemsetAsync(h->cosync, 0, (size_t)(std::max(h->S, h->S_sym) + 1) * sizeof(unsigned), stream()));
-    if (!useimg && h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));   // (image path: recorded below, around the whole pipeline)
+    MSM_HIP_CHECK(hipMemsetAsync(h->cosync, 0, (size_t)(std::max(h->S, g.S_sym) + 1) * sizeof(unsigned), stream()));
+    if (!pl.img() && h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));   // (image paths: recorded around the whole pipeline)
     h->last_fused = 0;
     h->last_carried = 0;
-    if (usefused && img_groups > 0 && img_groups / 2 < 0x7fffffffLL) {
-        // ONE launch over every K-step of the call: step records from the chunk table, then the fused kernel
-        const bool x2 = h->mode == MSM_TICA_BF16X2;
-        const long long nsteps = x2 ? img_groups / 2 : img_groups / 4;
-        int rc = h->imgsteps.reserve((size_t)nsteps * sizeof(ImgStep));
-        if (rc) return rc;
-        if (h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));
-        hipLaunchKernelGGL(tica_img_steps_kernel, dim3((unsigned)P.nchunks), dim3(64), 0, stream(), P.chunks, (long long)ld * 2, h->lag, x2 ? 1 : 0,
-                           h->imgsteps.as<ImgStep>());
-        MSM_HIP_CHECK(hipGetLastError());
-        ImgFusedArgs FA;
-        memset(&FA, 0, sizeof(FA));
-        FA.steps = h->imgsteps.as<ImgStep>();
-        FA.shift = P.shift;
-        FA.row_bytes = (long long)ld * 2;
-        FA.lag_bytes = (long long)h->lag * (long long)ld * 2;
-        FA.nsteps = (int)nsteps;
-        FA.T = h->T;
-        FA.T2 = h->T2;
-        FA.ntiles_sym = h->ntiles_sym;
-        FA.ntile2 = h->ntile2;
-        FA.S = h->S_img;
-        FA.main_steps = img_main_steps(nsteps, h->img_grid, h->ntile2);
-        FA.kflush_steps = std::max(1, x2 ? P.kflush / 16 : 8 * P.kflush / 32);   // (the image path's merge interval)
-        FA.slabs = h->slabs_sym;
-        if (x2)
-            hipLaunchKernelGGL((tica_img_fused_kernel<true>), dim3((unsigned)h->img_grid), dim3(IMG_NT), IMG_FUSED_LDS, stream(), FA);
-        else
-            hipLaunchKernelGGL((tica_img_fused_kernel<false>), dim3((unsigned)h->img_grid), dim3(IMG_NT), IMG_FUSED_LDS, stream(), FA);
-        MSM_HIP_CHECK(hipGetLastError());
-        h->last_fused = 1;
-    } else if (useimg) {
-        // The image is produced and consumed in SUPER-CHUNKS through a ring that the library owns (runtime.hip, img_ring):
-        // tica_img_kernel packs as many chunks as the ring holds, tica_img_pp_kernel multiplies them, and so on, all on
-        // stream().  Round 3 packed the WHOLE input into a per-handle image first (2x - 4x the input bytes of scratch,
-        // reserved inside the timed fit).  (Packing super-chunk k + 1 WHILE super-chunk k is multiplied was built and
-        // measured this round -- CU-masked streams, the MFMA kernel on the other CUs -- and is slower than taking turns:
-        // the packing pass needs the whole chip's memory pipelines, 40 - 64 CUs deliver 1.0 - 1.6 TB/s)
-        const bool x2 = h->mode == MSM_TICA_BF16X2;
-        const int Fp = h->T2 * 256;
-        ImgRing* ring = img_ring();
-        if (!ring) return MSM_ERR_HIP;
-        const int nimg = x2 ? 4 : 2;
-        const size_t gbytes = (size_t)Fp * 16;                                  // one 8-pair group of ONE image
-        const long long max_chunk_groups = ceil_div(kc, 32) * 4;
-        const std::vector<TicaChunk>& tab = img_tab;
-        // Round 6, the CARRIED pack (tica_img_dev.h): the multiply of super-chunk k packs super-chunk k + 1 into the other
-        // half of the ring in its load role; only the first (short) super-chunk takes the pre-pass kernel.  Whole 256-feature
-        // panels of 16-byte aligned rows, launches of more than one super-chunk, and few enough items per multiply step: a
-        // workgroup starts a quad of items in one multiply step and converts it in the next, so rho = (quads per pack step) /
-        // (units x multiply steps per pack step) is the share of its steps that carry when two consecutive super-chunks are
-        // equally long -- beyond ~0.9 the drain loop would do the packing with the matrix pipes idle (float32 rows of 256
-        // features in mode bf16).  MSM_TICA_IMG_CARRY=0 restores pack / multiply turns.
-        // Default from 1,024 features (bf16x2: 512), where it wins with the folded column sums (scripts/carryabl.py, profiles/r06_carry.txt:
-        // fit of 1M x 2048 bfloat16 rows 11.1 -> 10.5 ms, bf16x2 32.8 -> 28.8 ms; 768 features 7.15 -> 7.31 ms: the items' fp64
-        // column sums cost what the overlap saves); MSM_TICA_IMG_CARRY=1 forces it at any width it can run.
-        bool carry = h->F % 256 == 0 && ((long long)ld * dtype_bytes) % 16 == 0 && h->ntile2 <= h->img_grid;
-        bool prepass_all = false;   // MSM_TICA_IMG_CARRY=2 (A/B switch of the tests): the carried pack's super-chunks and ring halves, every one packed by the pre-pass kernel
-        {
-            const char* ce = getenv("MSM_TICA_IMG_CARRY");
-            if (ce && atoi(ce) == 0) carry = false;
-            if (!ce && h->F < (h->mode == MSM_TICA_BF16X2 ? 512 : 1024)) carry = false;   // (bf16x2: three times the multiply to hide behind -- 768 features 18.3 -> 16.0 ms, 512 15.4 -> 13.7 ms)
-            if (ce && atoi(ce) == 2) prepass_all = true;
-            for (size_t c = 0; c < tab.size() && carry; ++c)
-                if (((uintptr_t)tab[c].base) & 15) carry = false;
-        }
-        const int cy_nb = Fp / (dtype_bytes == 2 ? 64 : 32);
-        const double rho = 1.0 * cy_nb / (4.0 * h->ntile2 * (x2 ? 2 : 1));
-        if (rho > 0.9) carry = false;
-        long long slot_groups = (long long)((carry ? ring->bytes / 2 : ring->bytes) / (gbytes * nimg));
-        slot_groups -= slot_groups % 4;
-        if (carry && (slot_groups < 2 * max_chunk_groups || img_groups <= 2 * max_chunk_groups)) {   // (nothing to take turns with)
-            carry = false;
-            slot_groups = (long long)(ring->bytes / (gbytes * nimg));
-            slot_groups -= slot_groups % 4;
-        }
-        if (slot_groups < max_chunk_groups)
-            return fail(MSM_ERR_INVALID, "bf16 image ring too small for %d features (MSM_TICA_IMG_RING_MB)", h->F);
-        const size_t one = (size_t)slot_groups * gbytes;                        // bytes of one image inside the ring (half)
-        // super-chunks: whole chunks, as many as a slot holds; carried: the first one short (its pre-pass is the only one
-        // the matrix pipes wait for) but long enough to carry the second, and at most an eighth of the launch each so that
-        // short launches overlap as well
-        struct SuperChunk { size_t c0, c1; long long g0, g1; };
-        std::vector<SuperChunk> scs;
-        {
-            long long cap = slot_groups;
-            if (carry) {
-                long long want = ceil_div(ceil_div(img_groups, 8), 4) * 4;
-                want = std::max<long long>(want, 4 * max_chunk_groups);
-                cap = std::min(cap, want);
-            }
-            const long long first_cap = carry ? std::max<long long>(max_chunk_groups, (long long)(cap * std::max(0.25, std::min(1.0, 1.15 * rho)))) : cap;
-            for (size_t c0 = 0; c0 < tab.size() && img_groups > 0;) {
-                const long long lim = (carry && scs.empty()) ? first_cap : cap;
-                SuperChunk sc;
-                sc.c0 = c0;
-                sc.g0 = tab[c0].g0;
-                sc.c1 = c0;
-                sc.g1 = sc.g0;
-                while (sc.c1 < tab.size()) {
-                    const long long ge = sc.c1 + 1 < tab.size() ? tab[sc.c1 + 1].g0 : img_groups;
-                    if (ge - sc.g0 > lim && sc.c1 > c0) break;
-                    if (ge - sc.g0 > slot_groups) break;
-                    sc.g1 = ge;
-                    ++sc.c1;
-                }
-                scs.push_back(sc);
-                c0 = sc.c1;
-            }
-            if (scs.size() < 2) carry = false;
-        }
-        if (h->ev0) MSM_HIP_CHECK(hipEventRecord(h->ev0, stream()));
-        if (carry) {
-            // the launch's 32-pair step records (the table the fused kernel uses, with this launch's row size)
-            int rc = h->imgsteps.reserve((size_t)(img_groups / 4) * sizeof(ImgStep));
-            if (rc) return rc;
-            hipLaunchKernelGGL(tica_img_steps_kernel, dim3((unsigned)P.nchunks), dim3(64), 0, stream(), P.chunks, (long long)ld * dtype_bytes, h->lag, 0,
-                               h->imgsteps.as<ImgStep>());
-            MSM_HIP_CHECK(hipGetLastError());
-            if (fold) {
-                long long np_max = 0;
-                for (const SuperChunk& sc : scs) np_max = std::max(np_max, (sc.g1 - sc.g0) / 4);
-                if ((rc = h->colsteps.reserve((size_t)np_max * Fp * sizeof(double)))) return rc;
-            }
-        }
-        h->last_carried = 0;
-        for (size_t k = 0; k < scs.size(); ++k) {
-            const SuperChunk& sc = scs[k];
-            char* const half = ring->p + ((carry && (k & 1)) ? ring->bytes / 2 : 0);
-            if (!carry || k == 0 || prepass_all) {
-                ImgArgs IA;
-                memset(&IA, 0, sizeof(IA));
-                IA.chunks = P.chunks + sc.c0;
-                IA.nchunks = (long long)(sc.c1 - sc.c0);
-                IA.ld = ld;
-                IA.F = h->F;
-                IA.Fp = Fp;
-                IA.lag = h->lag;
-                IA.dtype_bytes = dtype_bytes;
-                IA.shift = P.shift;
-                IA.colA = fold ? h->foldimg.as<double>() + sc.c0 * (size_t)h->F : nullptr;
-                IA.g_off = sc.g0;
-                IA.u_hi = reinterpret_cast<bf16x8*>(half);
-                IA.d_hi = reinterpret_cast<bf16x8*>(half + one);
-                IA.u_mid = x2 ? reinterpret_cast<bf16x8*>(half + 2 * one) : nullptr;
-                IA.d_mid = x2 ? reinterpret_cast<bf16x8*>(half + 3 * one) : nullptr;
-                const dim3 g1((unsigned)(sc.c1 - sc.c0), (unsigned)h->T2);
-                if (x2)
-                    hipLaunchKernelGGL(tica_img_kernel<true>, g1, dim3(256), 0, stream(), IA);
-                else
-                    hipLaunchKernelGGL(tica_img_kernel<false>, g1, dim3(256), 0, stream(), IA);
-                MSM_HIP_CHECK(hipGetLastError());
-            }
-            ImgMfmaArgs MA;
-            memset(&MA, 0, sizeof(MA));
-            MA.u_hi = reinterpret_cast<bf16x8*>(half);
-            MA.d_hi = reinterpret_cast<bf16x8*>(half + one);
-            MA.u_mid = x2 ? reinterpret_cast<bf16x8*>(half + 2 * one) : nullptr;
-            MA.d_mid = x2 ? reinterpret_cast<bf16x8*>(half + 3 * one) : nullptr;
-            MA.nsteps = x2 ? (sc.g1 - sc.g0) / 2 : (sc.g1 - sc.g0) / 4;
-            MA.Fp = Fp;
-            MA.T = h->T;
-            MA.T2 = h->T2;
-            MA.ntiles_sym = h->ntiles_sym;
-            MA.ntile2 = h->ntile2;
-            MA.S = h->S_img;
-            MA.main_steps = img_main_steps(MA.nsteps, h->img_grid, h->ntile2);
-            // fp32 partials: bf16 inputs carry 8 significant bits, their products' partial sums can run 8x longer than the
-            // fp32 kernels' before the merge costs accuracy that matters (stated tolerance of the mode: 1e-3)
-            MA.kflush_steps = std::max(1, x2 ? P.kflush / 16 : 8 * P.kflush / 32);
-            MA.slabs = h->slabs_sym;
-            const bool carries = carry && !prepass_all && k + 1 < scs.size();
-            if (carries) {
-                const SuperChunk& nx = scs[k + 1];
-                char* const other = ring->p + ((k & 1) ? 0 : ring->bytes / 2);
-                MA.cy.psteps = h->imgsteps.as<ImgStep>() + nx.g0 / 4;
-                MA.cy.shift = P.shift;
-                MA.cy.u_hi = reinterpret_cast<bf16x8*>(other);
-                MA.cy.d_hi = reinterpret_cast<bf16x8*>(other + one);
-                MA.cy.u_mid = x2 ? reinterpret_cast<bf16x8*>(other + 2 * one) : nullptr;
-                MA.cy.d_mid = x2 ? reinterpret_cast<bf16x8*>(other + 3 * one) : nullptr;
-                MA.cy.colS = fold ? h->colsteps.as<double>() : nullptr;
-                MA.cy.row_bytes = (long long)ld * dtype_bytes;
-                MA.cy.lag_bytes = (long long)h->lag * ld * dtype_bytes;
-                MA.cy.np = (int)((nx.g1 - nx.g0) / 4);
-                MA.cy.nb = cy_nb;
-                // a workgroup's multiply steps / its quads (every workgroup multiplies ~ nsteps x units / grid steps)
-                const long long wsteps = MA.nsteps * h->ntile2 / h->img_grid;
-                const long long wquads = ceil_div(ceil_div((long long)MA.cy.np * cy_nb, 4), h->img_grid);
-                MA.cy.stride = (int)std::max<long long>(1, wsteps / std::max<long long>(1, wquads));
-                {
-                    const char* ae = getenv("MSM_TICA_IMG_CARRY_ABL");   // timing ablations only (tica_img_dev.h, img_carry_phase)
-                    MA.cy.pad = ae ? atoi(ae) : 0;
-                }
-                h->last_carried = 1;
-            }
-#define MSM_IMG_PP_LAUNCH(X2_, CY_) \
-            hipLaunchKernelGGL((tica_img_pp_kernel<X2_, IMG_LAG, false, 0, CY_>), dim3((unsigned)h->img_grid), dim3(IMG_NT), (CY_) ? IMG_PP_CARRY_LDS : IMG_PP_LDS, stream(), MA)
-            if (!carries) {
-                if (x2) MSM_IMG_PP_LAUNCH(true, 0);
-                else MSM_IMG_PP_LAUNCH(false, 0);
-            } else if (dtype_bytes == 2) {
-                if (x2) MSM_IMG_PP_LAUNCH(true, 2);
-                else MSM_IMG_PP_LAUNCH(false, 2);
-            } else {
-                if (x2) MSM_IMG_PP_LAUNCH(true, 4);
-                else MSM_IMG_PP_LAUNCH(false, 4);
-            }
-#undef MSM_IMG_PP_LAUNCH
-            MSM_HIP_CHECK(hipGetLastError());
-            if (carries && fold) {
-                const SuperChunk& nx = scs[k + 1];
-                hipLaunchKernelGGL(tica_img_colsum_steps_kernel, dim3((unsigned)(nx.c1 - nx.c0), (unsigned)ceil_div(h->F, 256)), dim3(256), 0, stream(),
-                                   P.chunks + nx.c0, (long long)(nx.c1 - nx.c0), nx.g0, nx.g1, h->colsteps.as<double>(), h->F, Fp,
-                                   h->foldimg.as<double>() + nx.c0 * (size_t)h->F);
-                MSM_HIP_CHECK(hipGetLastError());
-            }
-        }
-    } else if (usesymw) {
-        SymwArgs WA;
-        WA.T = P;
-        WA.slabs = h->slabs_w;
-        const bool vec = h->F >= (symw64 ? 2 : 4);   // 16-byte pieces at any 4-byte alignment; rows of 1-3 floats (a single double) element by element
-        if (symw64) {
-            switch (h->symw_var) {
-#define MSM_SYMW_LAUNCH64(CFG)                                                                                       \
-                if (vec) hipLaunchKernelGGL((tica_symw_f64_kernel<CFG, true>), dim3(G), dim3(CFG::NTH), CFG::LDS64, stream(), WA); \
-                else hipLaunchKernelGGL((tica_symw_f64_kernel<SymwA, false>), dim3(G), dim3(SymwA::NTH), SymwA::LDS64, stream(), WA); \
-                break;
-                case 0: MSM_SYMW_LAUNCH64(SymwA)
-                case 1: MSM_SYMW_LAUNCH64(SymwB)
-                case 2: MSM_SYMW_LAUNCH64(SymwC)
-                case 6: MSM_SYMW_LAUNCH64(SymwG)
-                default: MSM_SYMW_LAUNCH64(SymwD)
-#undef MSM_SYMW_LAUNCH64
-            }
-        } else
-        switch (h->symw_var) {
-#define MSM_SYMW_LAUNCH(CFG)                                                                                      \
-            if (vec) hipLaunchKernelGGL((tica_symw_f32_kernel<CFG, true>), dim3(G), dim3(CFG::NTH), CFG::LDS, stream(), WA); \
-            else hipLaunchKernelGGL((tica_symw_f32_kernel<SymwA, false>), dim3(G), dim3(SymwA::NTH), SymwA::LDS, stream(), WA); \
+    switch (pl.path) {
+        case TICA_IMG_FUSED:   // (a launch of more K-steps than an int counts goes through the ring)
+            rc = a.img_groups > 0 && a.img_groups / 2 < 0x7fffffffLL ? launch_img_fused(a) : launch_img_ring(a);
             break;
-            case 0: MSM_SYMW_LAUNCH(SymwA)
-            case 1: MSM_SYMW_LAUNCH(SymwB)
-            case 2: MSM_SYMW_LAUNCH(SymwC)
-            case 3: MSM_SYMW_LAUNCH(SymwD)
-            case 4: MSM_SYMW_LAUNCH(SymwE)
-            case 6: MSM_SYMW_LAUNCH(SymwG)
-            case 7: MSM_SYMW_LAUNCH(SymwH)
-            default: MSM_SYMW_LAUNCH(SymwF)
-#undef MSM_SYMW_LAUNCH
-        }
-        h->symw_used = std::max(h->symw_used, (int)std::min<long long>(G, P.nchunks));
-    } else if (usesym) {
-        if (symrem) {
-            if (fold)
-                hipLaunchKernelGGL((tica_sym_f32_kernel<false, true, true>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-            else if (h->F % TM == 0)
-                hipLaunchKernelGGL((tica_sym_f32_kernel<false, false, true>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-            else
-                hipLaunchKernelGGL((tica_sym_f32_kernel<true, false, true>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-        } else if (fold)
-            hipLaunchKernelGGL((tica_sym_f32_kernel<false, true>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-        else if (h->F % TM == 0)
-            hipLaunchKernelGGL((tica_sym_f32_kernel<false, false>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-        else
-            hipLaunchKernelGGL((tica_sym_f32_kernel<true, false>), dim3(G), dim3(NT), LDSSYM, stream(), P);
-    } else if (use32) {
-        if (aligned && h->F % TM == 0)
-            hipLaunchKernelGGL((tica_mfma_f32_kernel<true, false>), dim3(G), dim3(NT), LDS32, stream(), P);
-        else if (aligned)
-            hipLaunchKernelGGL((tica_mfma_f32_kernel<true, true>), dim3(G), dim3(NT), LDS32, stream(), P);
-        else
-            hipLaunchKernelGGL((tica_mfma_f32_kernel<false, true>), dim3(G), dim3(NT), LDS32, stream(), P);
-    } else if (dtype_bytes == 4) {
-        hipLaunchKernelGGL(tica_mfma_f64_kernel<float>, dim3(G), dim3(NT), LDS64, stream(), P);
-    } else {
-        hipLaunchKernelGGL(tica_mfma_f64_kernel<double>, dim3(G), dim3(NT), LDS64, stream(), P);
+        case TICA_IMG_RING: rc = launch_img_ring(a); break;
+        case TICA_SYMW:
+        case TICA_SYMW64: rc = launch_symw(a); break;
+        case TICA_SYM: rc = launch_sym(a); break;
+        case TICA_CG32: rc = launch_cg32(a); break;
+        default: rc = launch_cg64(a); break;
     }
+    if (rc) return rc;
     MSM_HIP_CHECK(hipGetLastError());
     if (h->ev1) {
         MSM_HIP_CHECK(hipEventRecord(h->ev1, stream()));
@@ -836,41 +852,15 @@ int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t
         const int rch = (*after_launch)();
         if (rch) return rch;
     }
-    if (fold) {
-        // 3') temporary partials -> [left sums | right sums] per slot, finite check of the folded sums
-        if (useimg)
-            hipLaunchKernelGGL(tica_fold_fix_img_kernel, dim3((unsigned)ceil_div((size_t)NCB * h->F, 256)), dim3(256), 0, stream(),
-                               h->coltmp, h->foldimg.as<double>(), h->F, P.nchunks, h->flag);
-        else
-            hipLaunchKernelGGL(tica_fold_fix_kernel, dim3((unsigned)ceil_div((size_t)NCB * h->F, 256)), dim3(256), 0, stream(),
-                               h->coltmp, h->fold, h->F, h->S_sym, h->flag);
-        MSM_HIP_CHECK(hipGetLastError());
-        if (check_finite) {
-            int f[2] = {0, 0};
-            MSM_HIP_CHECK(hipMemcpyAsync(f, h->flag, sizeof(f), hipMemcpyDeviceToHost, stream()));
-            MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-            if (f[0]) {   // undo the launch: the slabs as they were, nothing of it in the column sums or the shift
-                if (snapshot)
-                    MSM_HIP_CHECK(hipMemcpyAsync(h->slabs_sym, h->snap.p, slab_bytes, hipMemcpyDeviceToDevice, stream()));
-                else
-                    MSM_HIP_CHECK(hipMemsetAsync(h->slabs_sym, 0, slab_bytes, stream()));
-                MSM_HIP_CHECK(hipMemsetAsync(h->coltmp, 0, (size_t)NCB * 2 * h->F * sizeof(double), stream()));
-                MSM_HIP_CHECK(hipMemsetAsync(h->flag, 0, sizeof(int), stream()));
-                MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-                return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
-            }
-        }
-        int rc = shift_and_merge(0);
-        if (rc) return rc;
-    }
-    if (usesym) h->slabs_dirty = true;
-    else if (!usesymw) h->cg_dirty = true;
-    h->last_folded = fold;
+    if (pl.fold && (rc = fold_fixup(a))) return rc;
+    if (pl.sym_slabs()) h->slabs_dirty = true;
+    else if (!pl.symw()) h->cg_dirty = true;
+    h->last_folded = pl.fold;
     for (msm_idx_t s = 0; s < n_seq; ++s) {
-        const SegInfo g = seg_of(s);
-        if (g.len > h->lag && g.oe > g.ob) {
-            h->n_obs += g.oe - g.ob;       // summed over the ranks sharing a trajectory this is its length
-            h->n_seq += (g.ob == 0) ? 1 : 0;  // ... and the rank owning row 0 counts the sequence
+        const SegInfo t = L.seg(s);
+        if (L.valid(t, g.lag)) {
+            h->n_obs += t.oe - t.ob;       // summed over the ranks sharing a trajectory this is its length
+            h->n_seq += (t.ob == 0) ? 1 : 0;  // ... and the rank owning row 0 counts the sequence
         }
     }
     return MSM_OK;
@@ -879,26 +869,26 @@ int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t
 // queues slabs / column partials / base -> h->packed (raw moments, un-shifted); no synchronisation
 int tica_export_queue(msm_tica* h)
 {
-    const size_t total = 2 * (size_t)h->F * h->F + 2 * (size_t)h->F;
+    const size_t total = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
     hipLaunchKernelGGL(tica_export_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream(),
-                       h->slabs, h->colpart, h->base, h->packed, h->F, h->T, h->ntiles, h->cg_dirty ? h->S : 0);
-    hipLaunchKernelGGL(tica_export_cols_kernel, dim3((unsigned)ceil_div(2 * (int64_t)h->F, 64)), dim3(256), 0, stream(), h->colpart, h->base,
-                       h->packed, h->F);
+                       h->slabs, h->colpart, h->base, h->packed, h->g.F, h->g.T, h->g.ntiles, h->cg_dirty ? h->S : 0);
+    hipLaunchKernelGGL(tica_export_cols_kernel, dim3((unsigned)ceil_div(2 * (int64_t)h->g.F, 64)), dim3(256), 0, stream(), h->colpart, h->base,
+                       h->packed, h->g.F);
     MSM_HIP_CHECK(hipGetLastError());
-    if (h->sym && h->slabs_sym) {
-        hipLaunchKernelGGL(tica_export_sym_kernel, dim3((unsigned)ceil_div((size_t)h->ntiles_sym * TM * TM, 256)), dim3(256), 0, stream(),
-                           h->slabs_sym, h->packed, h->F, h->T, h->ntiles_sym, h->S_sym);
+    if (h->g.sym && h->slabs_sym) {
+        hipLaunchKernelGGL(tica_export_sym_kernel, dim3((unsigned)ceil_div((size_t)h->g.ntiles_sym * TM * TM, 256)), dim3(256), 0, stream(),
+                           h->slabs_sym, h->packed, h->g.F, h->g.T, h->g.ntiles_sym, h->g.S_sym);
         MSM_HIP_CHECK(hipGetLastError());
     }
     if (h->symw_used > 0) {
-        hipLaunchKernelGGL(tica_export_symw_kernel, dim3((unsigned)ceil_div((size_t)h->F * h->F, 256)), dim3(256), 0, stream(),
-                           h->slabs_w, h->packed, h->F, h->symw_FP, h->symw_W, h->symw_IL, h->symw_used);
+        hipLaunchKernelGGL(tica_export_symw_kernel, dim3((unsigned)ceil_div((size_t)h->g.F * h->g.F, 256)), dim3(256), 0, stream(),
+                           h->slabs_w, h->packed, h->g.F, h->symw_FP, h->symw_W, h->symw_IL, h->symw_used);
         MSM_HIP_CHECK(hipGetLastError());
     }
     if (h->have_shift) {  // restore the raw moments from the shifted ones (fp64)
-        const size_t ff2 = 2 * (size_t)h->F * h->F;
+        const size_t ff2 = 2 * (size_t)h->g.F * h->g.F;
         hipLaunchKernelGGL(tica_unshift_kernel, dim3((unsigned)ceil_div(ff2, 256)), dim3(256), 0, stream(), h->packed,
-                           h->shsum, h->shift, (double)h->n_sh, (double)h->nw_sh, h->F, h->sym);
+                           h->shsum, h->shift, (double)h->n_sh, (double)h->nw_sh, h->g.F, h->g.sym);
         MSM_HIP_CHECK(hipGetLastError());
     }
     return MSM_OK;
@@ -906,7 +896,7 @@ int tica_export_queue(msm_tica* h)
 
 int tica_export_device(msm_tica* h)
 {
-    const size_t total = 2 * (size_t)h->F * h->F + 2 * (size_t)h->F;
+    const size_t total = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
     {
         const int rcq = tica_export_queue(h);
         if (rcq) return rcq;
@@ -919,6 +909,120 @@ int tica_export_device(msm_tica* h)
 
 }  // namespace
 
+// whole-matrix sum/difference kernel: the variant of the width, its kernels' resident workgroups (float rows, and
+// float64 rows up to 128 features unless MSM_TICA_SYMW64=0: the same variant on doubles, the same slabs)
+static int create_symw(msm_tica* h)
+{
+    TicaGeom& g = h->g;
+    g.symw_var = tica_symw_variant(g.F);
+    int rc = MSM_OK, slots = INT_MAX, slots64 = INT_MAX;
+    const char* e64 = getenv("MSM_TICA_SYMW64");   // (A/B switch of the tests)
+    const bool want64 = g.F <= 128 && !(e64 && atoi(e64) == 0);
+    symw_visit(g.symw_var, [&](auto cfg) {
+        using Cfg = decltype(cfg);
+        h->symw_FP = Cfg::FP;
+        h->symw_W = Cfg::W;
+        h->symw_IL = Cfg::IL;
+        g.symw_KS = Cfg::KS;
+        // rows of 1-3 floats (a single double) go element by element through SymwA
+        if (g.F >= 4) rc = prep_kernel(tica_symw_f32_kernel<Cfg, true>, Cfg::NTH, Cfg::LDS, &slots);
+        else rc = prep_kernel(tica_symw_f32_kernel<SymwA, false>, SymwA::NTH, SymwA::LDS, &slots);
+        if constexpr (symw_has64<Cfg>) {
+            if (rc || !want64) return;
+            if (g.F >= 2) rc = prep_kernel(tica_symw_f64_kernel<Cfg, true>, Cfg::NTH, Cfg::LDS64, &slots64, 0);
+            else rc = prep_kernel(tica_symw_f64_kernel<SymwA, false>, SymwA::NTH, SymwA::LDS64, &slots64, 0);
+        }
+    });
+    if (rc) return rc;
+    if (slots64 != INT_MAX && slots64 >= 1) {   // (a variant that is not resident on doubles leaves them to the fp64 C/G kernel)
+        g.symw64 = 1;
+        g.symw_S64 = slots64;
+    }
+    g.symw_S = slots;
+    g.symw = 1;
+    g.sym = 1;   // the exported lagged moment is the symmetrised one
+    return MSM_OK;
+}
+
+// symmetric fp32 kernel (H/D blocks of the upper tiles): two 64-KiB workgroups per CU
+static int create_sym(msm_tica* h)
+{
+    TicaGeom& g = h->g;
+    int rc = MSM_OK, slots = INT_MAX;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, false>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<true, false>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, true>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, false, true>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<true, false, true>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, true, true>, NT, LDSSYM, &slots))) return rc;
+    g.sym_cohorts = slots / g.ntiles_sym;
+    g.sym = g.sym_cohorts >= 1;  // at least one whole cohort resident (F <= 3968 on 256 CUs), else the C/G kernel
+    // remainder cohort: the slots beyond the whole cohorts, when they are worth a launch flavour of their own --
+    // at least a sixteenth of the chip and at most three rounds over the tiles (2,048 features: 104 of 512 slots,
+    // two rounds; 512 features: 2 slots, not worth it)
+    const int R = slots - g.sym_cohorts * g.ntiles_sym;
+    const bool rem = g.sym && R * 16 >= slots && 3 * R >= g.ntiles_sym;
+    g.sym_grid = rem ? slots : g.sym_cohorts * g.ntiles_sym;
+    g.S_sym = g.sym_cohorts + (rem ? 1 : 0);
+    return MSM_OK;
+}
+
+// bf16 image path (256 x 256 tiles of H and D on the upper triangle, one 8-wave workgroup per CU)
+static int create_img(msm_tica* h)
+{
+    TicaGeom& g = h->g;
+    int rc = MSM_OK;
+    if ((rc = prep_kernel(tica_img_pp_kernel<false, IMG_LAG>, IMG_NT, IMG_PP_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_pp_kernel<true, IMG_LAG>, IMG_NT, IMG_PP_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_pp_kernel<false, IMG_LAG, false, 0, 2>, IMG_NT, IMG_PP_CARRY_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_pp_kernel<true, IMG_LAG, false, 0, 2>, IMG_NT, IMG_PP_CARRY_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_pp_kernel<false, IMG_LAG, false, 0, 4>, IMG_NT, IMG_PP_CARRY_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_pp_kernel<true, IMG_LAG, false, 0, 4>, IMG_NT, IMG_PP_CARRY_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_fused_kernel<false>, IMG_NT, IMG_FUSED_LDS, nullptr))) return rc;
+    if ((rc = prep_kernel(tica_img_fused_kernel<true>, IMG_NT, IMG_FUSED_LDS, nullptr))) return rc;
+    if (!img_ring()) return MSM_ERR_HIP;   // the process's image ring exists before any fit is timed
+    g.img_on = 1;
+    g.img_grid = std::max(num_cus(), g.ntile2);   // one workgroup per CU: whole cohorts + a remainder cohort (tica_img_dev.h)
+    g.S_img = g.img_grid / g.ntile2;
+    g.sym = 1;                 // the exported lagged moment is the symmetrised one
+    g.S_sym = g.S_img + 1;     // slab rows: the cohorts' and the remainder cohort's
+    g.sym_cohorts = g.S_img;
+    return MSM_OK;
+}
+
+// what a handle is made of: the kernels' resident slots -> cohorts per path (one resident round per launch)
+static int create_geometry(msm_tica* h)
+{
+    TicaGeom& g = h->g;
+    g.T = (int)ceil_div(g.F, TM);
+    g.ntiles = g.T * g.T + g.T * (g.T + 1) / 2;
+    g.T2 = (int)ceil_div(g.F, 256);
+    g.ntile2 = g.T2 * (g.T2 + 1);
+    int rc = MSM_OK, slots32 = INT_MAX, slots64 = INT_MAX;
+    if ((rc = prep_kernel(tica_mfma_f32_kernel<true, false>, NT, LDS32, &slots32))) return rc;
+    if ((rc = prep_kernel(tica_mfma_f32_kernel<true, true>, NT, LDS32, &slots32))) return rc;
+    if ((rc = prep_kernel(tica_mfma_f32_kernel<false, true>, NT, LDS32, &slots32))) return rc;
+    if ((rc = prep_kernel(tica_mfma_f64_kernel<float>, NT, LDS64, &slots64))) return rc;
+    if ((rc = prep_kernel(tica_mfma_f64_kernel<double>, NT, LDS64, &slots64))) return rc;
+    g.S32 = std::max(1, slots32 / g.ntiles);
+    g.S64 = std::max(1, slots64 / g.ntiles);
+    // MSM_TICA_SYM=0 (raw lagged moment wanted) leaves the C/G kernels in charge; MSM_TICA_SYMW=0 (A/B switch of the tests)
+    // the 128-wide sum/difference kernel where the whole-matrix one (fp32 mode, F <= 256) would run
+    const char* sym_env = getenv("MSM_TICA_SYM");
+    const char* symw_env = getenv("MSM_TICA_SYMW");
+    const bool sym_off = sym_env && atoi(sym_env) == 0, symw_off = symw_env && atoi(symw_env) == 0;
+    constexpr int tmax = 64;  // and one resident cohort must fit (create_sym)
+    if (g.mode == MSM_TICA_F32 && !sym_off && !symw_off && g.F <= 256) {
+        rc = create_symw(h);
+    } else {
+        g.ntiles_sym = g.T * (g.T + 1) / 2;
+        if (g.mode == MSM_TICA_F32 && !sym_off && g.T >= 2 && g.T <= tmax && g.F % 4 == 0) rc = create_sym(h);
+    }
+    if (rc) return rc;
+    if ((g.mode == MSM_TICA_BF16 || g.mode == MSM_TICA_BF16X2) && g.ntile2 <= num_cus()) rc = create_img(h);
+    return rc;
+}
+
 extern "C" {
 
 int msm_tica_create(msm_tica_t** out, msm_idx_t n_features, msm_idx_t lag_time, int mode)
@@ -929,202 +1033,49 @@ int msm_tica_create(msm_tica_t** out, msm_idx_t n_features, msm_idx_t lag_time, 
     if (mode < MSM_TICA_F32 || mode > MSM_TICA_BF16X2) return fail(MSM_ERR_INVALID, "unknown tica mode %d", mode);
     if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
     msm_tica* h = new msm_tica();
-    h->F = (int)n_features;
-    h->lag = (int)lag_time;
-    h->mode = mode;
-    h->T = (int)ceil_div(n_features, TM);
-    h->ntiles = h->T * h->T + h->T * (h->T + 1) / 2;
-    int slots32 = 0, slots64 = 0, rc;
-    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_mfma_f32_kernel<true, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32));
-    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_mfma_f32_kernel<true, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32));
-    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_mfma_f32_kernel<false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32));
-    {
-        // all three flavours must be resident in one round: size the cohorts by the tightest
-        int sa = 0, sb = 0, sc = 0;
-        if ((rc = query_slots(tica_mfma_f32_kernel<true, false>, LDS32, &sa))) { delete h; return rc; }
-        if ((rc = query_slots(tica_mfma_f32_kernel<true, true>, LDS32, &sb))) { delete h; return rc; }
-        if ((rc = query_slots(tica_mfma_f32_kernel<false, true>, LDS32, &sc))) { delete h; return rc; }
-        slots32 = sa < sb ? sa : sb;
-        slots32 = slots32 < sc ? slots32 : sc;
+    TicaGeom& g = h->g;
+    g.F = (int)n_features;
+    g.lag = (int)lag_time;
+    g.mode = mode;
+    g.shift_on = 1;
+    int rc = create_geometry(h);
+    if (rc) {
+        delete h;
+        return rc;
     }
-    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_mfma_f64_kernel<float>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS64));
-    MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_mfma_f64_kernel<double>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS64));
-    {
-        int sa = 0, sb = 0;
-        if ((rc = query_slots(tica_mfma_f64_kernel<float>, LDS64, &sa))) { delete h; return rc; }
-        if ((rc = query_slots(tica_mfma_f64_kernel<double>, LDS64, &sb))) { delete h; return rc; }
-        slots64 = sa < sb ? sa : sb;
-    }
-    // one resident round per launch: S cohorts of ntiles workgroups, per kernel flavour
-    h->S32 = slots32 / h->ntiles;
-    h->S64 = slots64 / h->ntiles;
-    if (h->S32 < 1) h->S32 = 1;
-    if (h->S64 < 1) h->S64 = 1;
-    {
-        // whole-matrix sum/difference kernel (round 6): fp32 mode, F <= 256.  MSM_TICA_SYM=0 (raw lagged moment wanted) and
-        // MSM_TICA_SYMW=0 (A/B switch of the tests) leave the 128-wide kernels of rounds 1-5 in charge.
-        const char* sym_env = getenv("MSM_TICA_SYM");
-        const char* symw_env = getenv("MSM_TICA_SYMW");
-        const bool off = (sym_env && atoi(sym_env) == 0) || (symw_env && atoi(symw_env) == 0);
-        if (mode == MSM_TICA_F32 && !off && n_features <= 256) {
-            int occ = 0;
-#define MSM_SYMW_SETUP(VAR, CFG)                                                                                  \
-            {                                                                                                     \
-                h->symw_var = VAR; h->symw_FP = CFG::FP; h->symw_W = CFG::W; h->symw_IL = CFG::IL; h->symw_KS = CFG::KS; \
-                MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_symw_f32_kernel<CFG, true>), \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)CFG::LDS));    \
-                MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tica_symw_f32_kernel<CFG, true>, CFG::NTH, CFG::LDS)); \
-            }
-            if (n_features <= 16) MSM_SYMW_SETUP(0, SymwA)
-            else if (n_features <= 32) MSM_SYMW_SETUP(1, SymwB)
-            else if (n_features <= 64) MSM_SYMW_SETUP(2, SymwC)
-            else if (n_features <= 96) MSM_SYMW_SETUP(6, SymwG)
-            else if (n_features <= 128) MSM_SYMW_SETUP(3, SymwD)
-            else if (n_features <= 160) MSM_SYMW_SETUP(7, SymwH)
-            else if (n_features <= 192) MSM_SYMW_SETUP(4, SymwE)
-            else MSM_SYMW_SETUP(5, SymwF)
-#undef MSM_SYMW_SETUP
-            if (n_features < 4) {
-                MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_symw_f32_kernel<SymwA, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SymwA::LDS));
-                MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tica_symw_f32_kernel<SymwA, false>, SymwA::NTH, SymwA::LDS));
-            }
-            if (occ < 1) occ = 1;
-            // float64 rows (F <= 128): the same variant on doubles, the same slabs; the launch grid is the smaller of the two
-            {
-                const char* e64 = getenv("MSM_TICA_SYMW64");   // (A/B switch of the tests)
-                if (n_features <= 128 && !(e64 && atoi(e64) == 0)) {
-                    int occ64 = 0;
-#define MSM_SYMW_SETUP64(CFG)                                                                                          \
-                    {                                                                                                  \
-                        MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_symw_f64_kernel<CFG, true>), \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CFG::LDS64)); \
-                        MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ64, tica_symw_f64_kernel<CFG, true>, CFG::NTH, CFG::LDS64)); \
-                    }
-                    if (n_features <= 16) MSM_SYMW_SETUP64(SymwA)
-                    else if (n_features <= 32) MSM_SYMW_SETUP64(SymwB)
-                    else if (n_features <= 64) MSM_SYMW_SETUP64(SymwC)
-                    else if (n_features <= 96) MSM_SYMW_SETUP64(SymwG)
-                    else MSM_SYMW_SETUP64(SymwD)
-#undef MSM_SYMW_SETUP64
-                    if (n_features < 2) {
-                        MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_symw_f64_kernel<SymwA, false>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SymwA::LDS64));
-                        MSM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ64, tica_symw_f64_kernel<SymwA, false>, SymwA::NTH, SymwA::LDS64));
-                    }
-                    if (occ64 >= 1) {
-                        h->symw64 = 1;
-                        h->symw_S64 = occ64 * num_cus();
-                    }
-                }
-            }
-            h->symw_S = occ * num_cus();
-            h->symw = 1;
-            h->sym = 1;   // the exported lagged moment is the symmetrised one
-        }
-    }
-    if (!h->symw) {
-        // symmetric fp32 kernel (H/D blocks of the upper tiles): two 64-KiB workgroups per CU
-        const char* sym_env = getenv("MSM_TICA_SYM");
-        const bool sym_off = sym_env && atoi(sym_env) == 0;
-        h->ntiles_sym = h->T * (h->T + 1) / 2;
-        constexpr int tmax = 64;  // and one resident cohort must fit (checked below)
-        if (mode == MSM_TICA_F32 && !sym_off && h->T >= 2 && h->T <= tmax && n_features % 4 == 0) {
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<false, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<true, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            int sa = 0, sb = 0, sc = 0;
-            if ((rc = query_slots(tica_sym_f32_kernel<false, false>, LDSSYM, &sa))) { delete h; return rc; }
-            if ((rc = query_slots(tica_sym_f32_kernel<true, false>, LDSSYM, &sb))) { delete h; return rc; }
-            if ((rc = query_slots(tica_sym_f32_kernel<false, true>, LDSSYM, &sc))) { delete h; return rc; }
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<false, false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<true, false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_sym_f32_kernel<false, true, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSSYM));
-            int sd = 0, se = 0, sf = 0;
-            if ((rc = query_slots(tica_sym_f32_kernel<false, false, true>, LDSSYM, &sd))) { delete h; return rc; }
-            if ((rc = query_slots(tica_sym_f32_kernel<true, false, true>, LDSSYM, &se))) { delete h; return rc; }
-            if ((rc = query_slots(tica_sym_f32_kernel<false, true, true>, LDSSYM, &sf))) { delete h; return rc; }
-            const int slots = std::min(std::min(std::min(sa, sb), sc), std::min(std::min(sd, se), sf));
-            h->sym_cohorts = slots / h->ntiles_sym;
-            h->sym = h->sym_cohorts >= 1;  // at least one whole cohort resident (F <= 3968 on 256 CUs), else the C/G kernel
-            // remainder cohort: the slots beyond the whole cohorts, when they are worth a launch flavour of their own --
-            // at least a sixteenth of the chip and at most three rounds over the tiles (2,048 features: 104 of 512 slots,
-            // two rounds; 512 features: 2 slots, not worth it)
-            const int R = slots - h->sym_cohorts * h->ntiles_sym;
-            const bool rem = h->sym && R * 16 >= slots && 3 * R >= h->ntiles_sym;
-            h->sym_grid = rem ? slots : h->sym_cohorts * h->ntiles_sym;
-            h->S_sym = h->sym_cohorts + (rem ? 1 : 0);
-        }
-    }
-    {
-        // bf16 image path (256 x 256 tiles of H and D on the upper triangle, one 8-wave workgroup per CU)
-        h->T2 = (int)ceil_div(n_features, 256);
-        h->ntile2 = h->T2 * (h->T2 + 1);
-        if ((mode == MSM_TICA_BF16 || mode == MSM_TICA_BF16X2) && h->ntile2 <= num_cus()) {
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<false, IMG_LAG>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<true, IMG_LAG>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<false, IMG_LAG, false, 0, 2>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_CARRY_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<true, IMG_LAG, false, 0, 2>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_CARRY_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<false, IMG_LAG, false, 0, 4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_CARRY_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_pp_kernel<true, IMG_LAG, false, 0, 4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_PP_CARRY_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_fused_kernel<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_FUSED_LDS));
-            MSM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tica_img_fused_kernel<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_FUSED_LDS));
-            if (!img_ring()) { delete h; return MSM_ERR_HIP; }   // the process's image ring exists before any fit is timed
-            h->img_on = 1;
-            h->img_grid = std::max(num_cus(), h->ntile2);   // one workgroup per CU: whole cohorts + a remainder cohort (tica_img_dev.h)
-            h->S_img = h->img_grid / h->ntile2;
-            h->sym = 1;                 // the exported lagged moment is the symmetrised one
-            h->S_sym = h->S_img + 1;    // slab rows: the cohorts' and the remainder cohort's
-            h->sym_cohorts = h->S_img;
-        }
-    }
-    h->S = std::max(h->S32, h->S64);  // slabs exist for the largest; unused ones stay zero
-    h->G = h->S * h->ntiles;
-    const size_t FF2 = 2 * (size_t)h->F * h->F + 2 * (size_t)h->F;
+    h->S = std::max(g.S32, g.S64);  // slabs exist for the largest; unused ones stay zero
+    h->G = h->S * g.ntiles;
+    const size_t FF2 = 2 * (size_t)g.F * g.F + 2 * (size_t)g.F;
+    const size_t wb = (size_t)g.symw_S * 2 * h->symw_FP * h->symw_FP * sizeof(double);
+    const size_t foldb = (size_t)(g.S_sym + FOLD_NB + 1) * g.F * sizeof(double);
     hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void**)&h->slabs, (size_t)h->G * TM * TM * sizeof(double));
-    if (e == hipSuccess && h->sym && !h->symw) e = hipMalloc((void**)&h->slabs_sym, (size_t)h->S_sym * h->ntiles_sym * 2 * TM * TM * sizeof(double));
-    if (e == hipSuccess && h->symw) {
-        const size_t wb = (size_t)h->symw_S * 2 * h->symw_FP * h->symw_FP * sizeof(double);
-        e = hipMalloc((void**)&h->slabs_w, wb);
+    auto alloc = [&](auto** p, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
+    };
+    alloc(&h->slabs, (size_t)h->G * TM * TM * sizeof(double));
+    if (g.sym && !g.symw) alloc(&h->slabs_sym, h->sym_slab_bytes());
+    if (g.symw) {
+        alloc(&h->slabs_w, wb);
         if (e == hipSuccess) e = hipMemsetAsync(h->slabs_w, 0, wb, stream());   // (once: a reset zeroes only the rows a launch has used)
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->base, FF2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->colpart, (size_t)NCB * 2 * h->F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->coltmp, (size_t)NCB * 2 * h->F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->packed, (FF2 + 2) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->flag, 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->dbg, 64 * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->cosync, (size_t)(std::max(h->S, h->S_sym) + 1) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->shift, (size_t)h->F * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->shsum, 3 * (size_t)h->F * sizeof(double));
-    if (e == hipSuccess && h->sym) e = hipMalloc((void**)&h->fold, (size_t)(h->S_sym + FOLD_NB + 1) * h->F * sizeof(double));
+    alloc(&h->base, FF2 * sizeof(double));
+    alloc(&h->colpart, h->colbytes());
+    alloc(&h->coltmp, h->colbytes());
+    alloc(&h->packed, (FF2 + 2) * sizeof(double));
+    alloc(&h->flag, 2 * sizeof(int));
+    alloc(&h->dbg, 64 * sizeof(long long));
+    alloc(&h->cosync, (size_t)(std::max(h->S, g.S_sym) + 1) * sizeof(unsigned));
+    alloc(&h->shift, (size_t)g.F * sizeof(float));
+    alloc(&h->shsum, 3 * (size_t)g.F * sizeof(double));
+    if (g.sym) alloc(&h->fold, foldb);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
     if (e != hipSuccess) {
         msm_tica_destroy(h);
         return fail(MSM_ERR_HIP, "msm_tica_create: hipMalloc failed: %s", hipGetErrorString(e));
     }
-    if (h->fold) (void)hipMemsetAsync(h->fold, 0, (size_t)(h->S_sym + FOLD_NB + 1) * h->F * sizeof(double), stream());
+    g.have_fold = h->fold != nullptr;
+    if (h->fold) (void)hipMemsetAsync(h->fold, 0, foldb, stream());
     rc = tica_zero(h);
     if (rc) {
         msm_tica_destroy(h);
@@ -1138,19 +1089,9 @@ int msm_tica_destroy(msm_tica_t* h)
 {
     if (!h) return MSM_OK;
     (void)hipStreamSynchronize(stream());
-    if (h->slabs) (void)hipFree(h->slabs);
-    if (h->slabs_sym) (void)hipFree(h->slabs_sym);
-    if (h->slabs_w) (void)hipFree(h->slabs_w);
-    if (h->base) (void)hipFree(h->base);
-    if (h->colpart) (void)hipFree(h->colpart);
-    if (h->coltmp) (void)hipFree(h->coltmp);
-    if (h->packed) (void)hipFree(h->packed);
-    if (h->flag) (void)hipFree(h->flag);
-    if (h->dbg) (void)hipFree(h->dbg);
-    if (h->cosync) (void)hipFree(h->cosync);
-    if (h->shift) (void)hipFree(h->shift);
-    if (h->shsum) (void)hipFree(h->shsum);
-    if (h->fold) (void)hipFree(h->fold);
+    for (void* p : {(void*)h->slabs, (void*)h->slabs_sym, (void*)h->slabs_w, (void*)h->base, (void*)h->colpart, (void*)h->coltmp,
+                    (void*)h->packed, (void*)h->flag, (void*)h->dbg, (void*)h->cosync, (void*)h->shift, (void*)h->shsum, (void*)h->fold})
+        if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->solve_pin) (void)hipHostFree(h->solve_pin);
@@ -1171,9 +1112,9 @@ static int tica_accumulate_any(msm_tica_t* h, const void* const* X_ptrs, const m
     if (!h) return fail(MSM_ERR_STATE, "null tica handle");
     if (n_seq < 0 || (n_seq > 0 && (!X_ptrs || !n_rows))) return fail(MSM_ERR_INVALID, "bad sequence table");
     if (dtype_bytes != 4 && dtype_bytes != 8 && dtype_bytes != 2) return fail(MSM_ERR_INVALID, "dtype_bytes must be 2 (bfloat16), 4 or 8");
-    if (dtype_bytes == 2 && !h->img_on)
-        return fail(MSM_ERR_INVALID, "bfloat16 trajectories need MSM_TICA_BF16 / MSM_TICA_BF16X2 mode (got mode %d)", h->mode);
-    if (ld < h->F) return fail(MSM_ERR_INVALID, "ld=%lld < n_features=%d", (long long)ld, h->F);
+    if (dtype_bytes == 2 && !h->g.img_on)
+        return fail(MSM_ERR_INVALID, "bfloat16 trajectories need MSM_TICA_BF16 / MSM_TICA_BF16X2 mode (got mode %d)", h->g.mode);
+    if (ld < h->g.F) return fail(MSM_ERR_INVALID, "ld=%lld < n_features=%d", (long long)ld, h->g.F);
     for (msm_idx_t s = 0; s < n_seq; ++s)
         if (n_rows[s] < 0 || (n_rows[s] > 0 && !X_ptrs[s])) return fail(MSM_ERR_INVALID, "bad sequence %lld", (long long)s);
     if (n_skipped) *n_skipped = 0;
@@ -1186,7 +1127,7 @@ static int tica_accumulate_any(msm_tica_t* h, const void* const* X_ptrs, const m
     // (round 5: 42.4 -> 50.0 GB/s on the bench's h2d_inclusive leg, 4.1 GB in 82 ms: 68 ms of copies + 1.6 ms per group of
     // launch / check / merge that the host cannot copy beside; pinned -> device alone delivers 56-57 GB/s here:
     // profiles/r05_h2d_rate.txt).  The Python layer hands a materialised list down whole for this reason.
-    const size_t row_bytes = (size_t)h->F * dtype_bytes;
+    const size_t row_bytes = (size_t)h->g.F * dtype_bytes;
     const size_t budget = (size_t)512 << 20;
     struct Group {
         msm_idx_t s = 0, e = 0;
@@ -1221,7 +1162,7 @@ static int tica_accumulate_any(msm_tica_t* h, const void* const* X_ptrs, const m
             char* d = h->staging.as<char>() + (size_t)which * half + off;
             g.dptrs[(size_t)(i - g.s)] = d;
             if (n_rows[i] > 0) {
-                if (ld == h->F) {
+                if (ld == h->g.F) {
                     int rcb = h2d_bulk(d, X_ptrs[i], (size_t)n_rows[i] * row_bytes, first);
                     if (rcb) return rcb;
                 } else {
@@ -1242,7 +1183,7 @@ static int tica_accumulate_any(msm_tica_t* h, const void* const* X_ptrs, const m
         if (more) nxt = plan(cur.e).first;
         const std::function<int()> hook = [&]() -> int { return copy_group(nxt, which ^ 1, false); };
         msm_idx_t sk = 0;
-        rc = tica_accumulate_device(h, cur.dptrs.data(), n_rows + cur.s, cur.e - cur.s, dtype_bytes, h->F, check_finite, &sk,
+        rc = tica_accumulate_device(h, cur.dptrs.data(), n_rows + cur.s, cur.e - cur.s, dtype_bytes, h->g.F, check_finite, &sk,
                                     segs ? segs + cur.s : nullptr, more ? &hook : nullptr);
         if (rc) {
             (void)hipStreamSynchronize(stream());   // (copies of the next group may be in flight into the staging buffer)
@@ -1284,10 +1225,10 @@ int msm_tica_accumulate_segments(msm_tica_t* h, const void* const* X_ptrs, const
             return fail(MSM_ERR_INVALID, "segment %lld: slice [%lld, %lld) is not inside a trajectory of %lld rows",
                         (long long)s, (long long)g.off, (long long)(g.off + n_rows[s]), (long long)g.len);
         if (g.oe > g.ob) {
-            const long long need = (g.oe + h->lag < g.len ? g.oe + h->lag : g.len);  // right halo
+            const long long need = (g.oe + h->g.lag < g.len ? g.oe + h->g.lag : g.len);  // right halo
             if (g.ob < g.off || need > g.off + n_rows[s])
                 return fail(MSM_ERR_INVALID, "segment %lld: owned rows [%lld, %lld) + lag %d need rows [%lld, %lld) but the slice holds [%lld, %lld)",
-                            (long long)s, (long long)g.ob, (long long)g.oe, h->lag, (long long)g.ob, need,
+                            (long long)s, (long long)g.ob, (long long)g.oe, h->g.lag, (long long)g.ob, need,
                             (long long)g.off, (long long)(g.off + n_rows[s]));
         }
         segs[(size_t)s] = g;
@@ -1318,7 +1259,7 @@ int msm_tica_nonfinite(msm_tica_t* h, int* flag)
 int msm_tica_lagged_symmetrised(msm_tica_t* h, int* flag)
 {
     if (!h || !flag) return fail(MSM_ERR_STATE, "null argument");
-    *flag = h->sym ? 1 : 0;
+    *flag = h->g.sym ? 1 : 0;
     return MSM_OK;
 }
 
@@ -1335,6 +1276,39 @@ int msm_tica_last_folded(msm_tica_t* h, int* flag)
 {
     if (!h || !flag) return fail(MSM_ERR_STATE, "null argument");
     *flag = h->last_folded ? 1 : 0;
+    return MSM_OK;
+}
+
+int msm_tica_plan(const int* geom, int dtype_bytes, msm_idx_t ld, const msm_idx_t* n_rows, msm_idx_t n_seq, int ptr_aligned16,
+                  int dims_aligned4, int fold_switch, int fused_switch, long long* out)
+{
+    if (!geom || !out || n_seq < 0 || (n_seq > 0 && !n_rows)) return fail(MSM_ERR_INVALID, "msm_tica_plan: bad argument");
+    TicaGeom g;
+    memcpy(&g, geom, sizeof(g));
+    if (!tica_geom_valid(g)) return fail(MSM_ERR_INVALID, "msm_tica_plan: not a handle's geometry");
+    TicaLaunch L;
+    L.dtype_bytes = dtype_bytes;
+    L.ld = ld;
+    L.n_seq = n_seq;
+    L.n_rows = n_rows;
+    L.ptr16 = (ptr_aligned16 & 1) != 0;
+    L.ptr16_all = (ptr_aligned16 & 2) != 0;
+    L.dims4 = dims_aligned4 != 0;
+    L.fold_switch = fold_switch;
+    L.fused_switch = fused_switch;
+    tica_plan_ints(tica_plan(g, L), out);
+    return MSM_OK;
+}
+
+int msm_tica_last_plan(msm_tica_t* h, long long* out)
+{
+    if (!h || !out) return fail(MSM_ERR_INVALID, "msm_tica_last_plan: null argument");
+    int gi[TICA_GEOM_INTS];
+    memcpy(gi, &h->g, sizeof(gi));
+    std::copy(gi, gi + TICA_GEOM_INTS, out);
+    tica_plan_ints(h->last_plan, out + TICA_GEOM_INTS);
+    out[TICA_GEOM_INTS + TICA_PLAN_INTS] = h->last_nchunks;
+    out[TICA_GEOM_INTS + TICA_PLAN_INTS + 1] = h->last_super;
     return MSM_OK;
 }
 
@@ -1384,7 +1358,7 @@ int msm_tica_export_packed(msm_tica_t* h, double* buf, int on_device)
 int msm_tica_import_packed(msm_tica_t* h, const double* buf, int on_device)
 {
     if (!h || !buf) return fail(MSM_ERR_STATE, "null argument");
-    const size_t FF2 = 2 * (size_t)h->F * h->F + 2 * (size_t)h->F;
+    const size_t FF2 = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
     long long keep_flag = 0;
     (void)keep_flag;
     int rc = tica_zero(h);
@@ -1406,11 +1380,11 @@ int msm_tica_export(msm_tica_t* h, double* C, double* G, double* s0, double* sta
     if (!h) return fail(MSM_ERR_STATE, "null tica handle");
     int rc = tica_export_device(h);
     if (rc) return rc;
-    const size_t FF = (size_t)h->F * h->F;
+    const size_t FF = (size_t)h->g.F * h->g.F;
     if (C) MSM_HIP_CHECK(hipMemcpyAsync(C, h->packed, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
     if (G) MSM_HIP_CHECK(hipMemcpyAsync(G, h->packed + FF, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    if (s0) MSM_HIP_CHECK(hipMemcpyAsync(s0, h->packed + 2 * FF, h->F * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    if (stau) MSM_HIP_CHECK(hipMemcpyAsync(stau, h->packed + 2 * FF + h->F, h->F * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    if (s0) MSM_HIP_CHECK(hipMemcpyAsync(s0, h->packed + 2 * FF, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    if (stau) MSM_HIP_CHECK(hipMemcpyAsync(stau, h->packed + 2 * FF + h->g.F, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
     if (n_observations) *n_observations = h->n_obs;
     if (n_sequences) *n_sequences = h->n_seq;
@@ -1423,11 +1397,11 @@ int msm_tica_import(msm_tica_t* h, const double* C, const double* G, const doubl
     if (!h || !C || !G || !s0 || !stau) return fail(MSM_ERR_STATE, "null argument");
     int rc = tica_zero(h);
     if (rc) return rc;
-    const size_t FF = (size_t)h->F * h->F;
+    const size_t FF = (size_t)h->g.F * h->g.F;
     MSM_HIP_CHECK(hipMemcpyAsync(h->base, C, FF * sizeof(double), hipMemcpyHostToDevice, stream()));
     MSM_HIP_CHECK(hipMemcpyAsync(h->base + FF, G, FF * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(h->base + 2 * FF, s0, h->F * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(h->base + 2 * FF + h->F, stau, h->F * sizeof(double), hipMemcpyHostToDevice, stream()));
+    MSM_HIP_CHECK(hipMemcpyAsync(h->base + 2 * FF, s0, h->g.F * sizeof(double), hipMemcpyHostToDevice, stream()));
+    MSM_HIP_CHECK(hipMemcpyAsync(h->base + 2 * FF + h->g.F, stau, h->g.F * sizeof(double), hipMemcpyHostToDevice, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
     h->n_obs = n_observations;
     h->n_seq = n_sequences;
@@ -1450,7 +1424,7 @@ struct SolveBufs {
 
 int solve_bufs(msm_tica* h, SolveBufs* b)
 {
-    const size_t F = (size_t)h->F, FF = F * F;
+    const size_t F = (size_t)h->g.F, FF = F * F;
     const int nblk = (int)ceil_div((int64_t)FF, 256);
     const size_t nd = 5 * FF + 13 * F + 4 + 2 * (size_t)nblk + 384 + 128 * F + subspace_work_doubles((int)F);
     int rc = h->solve.reserve(nd * sizeof(double) + (8 + F / 16 + 4) * sizeof(int));
@@ -1484,19 +1458,19 @@ int tica_reduce_device(msm_tica* h, double shrinkage, long long n_rblw, const do
 {
     int rc = solve_bufs(h, b);
     if (rc) return rc;
-    const long long npairs = h->n_obs - (long long)h->lag * h->n_seq;
+    const long long npairs = h->n_obs - (long long)h->g.lag * h->n_seq;
     if (h->n_obs <= 0 || npairs <= 0) return fail(MSM_ERR_STATE, "the model must be fit() before use");
     // the packed raw moments (slab sums, un-shifted) stay on the device
     if ((rc = tica_export_queue(h))) return rc;
     MSM_HIP_CHECK(hipGetLastError());
     MSM_HIP_CHECK(hipMemsetAsync(b->ints, 0, 8 * sizeof(int), stream()));
-    if (scale_host) MSM_HIP_CHECK(hipMemcpyAsync(b->scale, scale_host, h->F * sizeof(double), hipMemcpyHostToDevice, stream()));
+    if (scale_host) MSM_HIP_CHECK(hipMemcpyAsync(b->scale, scale_host, h->g.F * sizeof(double), hipMemcpyHostToDevice, stream()));
     hipLaunchKernelGGL(tica_finalise_kernel, dim3((unsigned)b->nblk), dim3(256), 0, stream(), h->packed,
-                       scale_host ? b->scale : (const double*)nullptr, 2.0 * (double)npairs, h->F, b->A, b->B, b->mu, b->part, b->ints);
-    hipLaunchKernelGGL(tica_rblw_kernel, dim3(1), dim3(256), 0, stream(), b->part, b->nblk, shrinkage, (double)n_rblw, h->F, b->scal);
-    hipLaunchKernelGGL(tica_shrink_kernel, dim3((unsigned)b->nblk), dim3(256), 0, stream(), b->B, b->scal, h->F);
+                       scale_host ? b->scale : (const double*)nullptr, 2.0 * (double)npairs, h->g.F, b->A, b->B, b->mu, b->part, b->ints);
+    hipLaunchKernelGGL(tica_rblw_kernel, dim3(1), dim3(256), 0, stream(), b->part, b->nblk, shrinkage, (double)n_rblw, h->g.F, b->scal);
+    hipLaunchKernelGGL(tica_shrink_kernel, dim3((unsigned)b->nblk), dim3(256), 0, stream(), b->B, b->scal, h->g.F);
     MSM_HIP_CHECK(hipGetLastError());
-    if ((rc = sygv_reduce_device(b->A, b->B, h->F, b->ints + 2, b->Winv, b->T))) return rc;
+    if ((rc = sygv_reduce_device(b->A, b->B, h->g.F, b->ints + 2, b->Winv, b->T))) return rc;
     h->reduced = true;
     return MSM_OK;
 }
@@ -1550,11 +1524,11 @@ int msm_tica_reduce(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, const dou
     SolveBufs b;
     int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
     if (rc) return rc;
-    const size_t FF = (size_t)h->F * h->F;
+    const size_t FF = (size_t)h->g.F * h->g.F;
     double scal[4];
     int ints[8];
     MSM_HIP_CHECK(hipMemcpyAsync(Cs, b.A, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(mu, b.mu, h->F * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    MSM_HIP_CHECK(hipMemcpyAsync(mu, b.mu, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipMemcpyAsync(scal, b.scal, sizeof(scal), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipMemcpyAsync(ints, b.ints, sizeof(ints), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
@@ -1565,12 +1539,12 @@ int msm_tica_solve_topk(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, const
                         double* vecs, double* Cs, double* mu, double* info, int* status)
 {
     if (!h || !vals || !vecs || !Cs || !mu || !status) return fail(MSM_ERR_STATE, "msm_tica_solve_topk: null argument");
-    if (h->F > 1024 || h->F < 128) return fail(MSM_ERR_INVALID, "msm_tica_solve_topk: need 128 <= n_features <= 1024");
+    if (h->g.F > 1024 || h->g.F < 128) return fail(MSM_ERR_INVALID, "msm_tica_solve_topk: need 128 <= n_features <= 1024");
     if (k < 1 || k > 16) return fail(MSM_ERR_INVALID, "msm_tica_solve_topk: need 1 <= k <= 16");
     SolveBufs b;
     int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
     if (rc) return rc;
-    const int n = h->F;
+    const int n = h->g.F;
     const size_t FF = (size_t)n * n;
     // Chebyshev-filtered subspace iteration (subspace.hip): a few short launch chains when the spectrum has the gap tICA is
     // run for; the reduced tICA matrix has its spectrum in [-1, 1].  When it does not converge (flat spectra: white-noise
@@ -1668,17 +1642,17 @@ int msm_tica_backsolve(msm_tica_t* h, const double* Y, msm_idx_t k, double* V)
 {
     if (!h || !Y || !V) return fail(MSM_ERR_STATE, "msm_tica_backsolve: null argument");
     if (!h->reduced) return fail(MSM_ERR_STATE, "msm_tica_backsolve: no reduced problem (call msm_tica_reduce first)");
-    if (k < 1 || k > h->F) return fail(MSM_ERR_INVALID, "msm_tica_backsolve: need 1 <= k <= n_features");
+    if (k < 1 || k > h->g.F) return fail(MSM_ERR_INVALID, "msm_tica_backsolve: need 1 <= k <= n_features");
     SolveBufs b;
     int rc = solve_bufs(h, &b);
     if (rc) return rc;
-    const size_t bytes = (size_t)k * h->F * sizeof(double);
+    const size_t bytes = (size_t)k * h->g.F * sizeof(double);
     MSM_HIP_CHECK(hipMemcpyAsync(b.Y, Y, bytes, hipMemcpyHostToDevice, stream()));
-    if (h->F <= 1024 && k <= 64) {
-        if ((rc = winv_back_device(b.Winv, h->F, b.Y, (int)k, b.S))) return rc;
+    if (h->g.F <= 1024 && k <= 64) {
+        if ((rc = winv_back_device(b.Winv, h->g.F, b.Y, (int)k, b.S))) return rc;
         MSM_HIP_CHECK(hipMemcpyAsync(V, b.S, bytes, hipMemcpyDeviceToHost, stream()));
     } else {
-        if ((rc = sygv_back_device(b.B, b.Y, h->F, (int)k))) return rc;
+        if ((rc = sygv_back_device(b.B, b.Y, h->g.F, (int)k))) return rc;
         MSM_HIP_CHECK(hipMemcpyAsync(V, b.Y, bytes, hipMemcpyDeviceToHost, stream()));
     }
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
@@ -1689,11 +1663,11 @@ int msm_tica_solve_device(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, con
                           double* vals, double* vecs, double* mu, double* info)
 {
     if (!h || !vals || !vecs || !mu) return fail(MSM_ERR_STATE, "msm_tica_solve_device: null argument");
-    if (k < 1 || k > h->F) return fail(MSM_ERR_INVALID, "msm_tica_solve_device: need 1 <= k <= n_features");
+    if (k < 1 || k > h->g.F) return fail(MSM_ERR_INVALID, "msm_tica_solve_device: need 1 <= k <= n_features");
     SolveBufs b;
     int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
     if (rc) return rc;
-    const int n = h->F;
+    const int n = h->g.F;
     if ((rc = syevd_device(b.A, n, b.D, b.E, b.ints + 3))) return rc;
     if ((rc = sygv_back_device(b.B, b.A + (size_t)(n - k) * n, n, (int)k))) return rc;
     hipLaunchKernelGGL(tica_top_pairs_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, stream(), b.A, b.D, n,
@@ -1739,16 +1713,14 @@ int msm_tica_export_sums(msm_tica_t* h, double* s0, double* stau)
     if (!h || !s0 || !stau) return fail(MSM_ERR_STATE, "null argument");
     int rc = tica_export_device(h);
     if (rc) return rc;
-    const size_t FF = (size_t)h->F * h->F;
-    MSM_HIP_CHECK(hipMemcpyAsync(s0, h->packed + 2 * FF, h->F * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(stau, h->packed + 2 * FF + h->F, h->F * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    const size_t FF = (size_t)h->g.F * h->g.F;
+    MSM_HIP_CHECK(hipMemcpyAsync(s0, h->packed + 2 * FF, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    MSM_HIP_CHECK(hipMemcpyAsync(stau, h->packed + 2 * FF + h->g.F, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
     return MSM_OK;
 }
 
 }  // extern "C"
-
-extern "C" {
 
 // ---- projection: parameters on the device (once per call) and the launches for one device-resident matrix
 struct ProjParams {
@@ -1759,6 +1731,44 @@ struct ProjParams {
     std::vector<double> muV, vp;   // host sources of the uploads: alive until the caller has synchronised
 };
 
+// host sources of the projection's uploads: muV = mean @ comps^T, and the components in blocks of 16 as panels Vp[F][16]
+// (feature-major, zero padded) for the fp64-MFMA path
+static void proj_host_params(const double* mean, const double* comps, msm_idx_t k, msm_idx_t n_features, std::vector<double>& muV,
+                             std::vector<double>& vp)
+{
+    muV.assign((size_t)k, 0.0);
+    vp.assign((size_t)ceil_div(k, 16) * n_features * 16, 0.0);
+    for (msm_idx_t c = 0; c < k; ++c) {
+        double sacc = 0.0;
+        for (msm_idx_t f = 0; f < n_features; ++f) {
+            sacc += mean[f] * comps[c * n_features + f];
+            vp[((size_t)(c / 16) * n_features + f) * 16 + (c % 16)] = comps[c * n_features + f];
+        }
+        muV[(size_t)c] = sacc;
+    }
+}
+
+// the fp64-MFMA projection, one launch of `grid` workgroups per block of 16 components: rows of X[n_rows][ldd] into outd, or
+// -- `tiles` -- one tile of up to 256 rows per workgroup
+template <typename T>
+static void proj_mfma_blocks(unsigned grid, const void* Xd, long long n_rows, msm_idx_t n_features, long long ldd, const double* dmean,
+                             const double* dVp, msm_idx_t k, double* outd, int* dflag, const ProjTile* tiles)
+{
+    for (msm_idx_t kb = 0; kb < ceil_div(k, 16); ++kb)
+        hipLaunchKernelGGL((tica_project_mfma_kernel<T>), dim3(grid), dim3(NT), 0, stream(), (const T*)Xd, n_rows, (int)n_features, ldd,
+                           dmean, dVp + (size_t)kb * n_features * 16, (int)std::min<msm_idx_t>(16, k - kb * 16), (int)(kb * 16), (int)k,
+                           outd, dflag, tiles);
+}
+static int proj_launch_mfma(int dtype_bytes, unsigned grid, const void* Xd, long long n_rows, msm_idx_t n_features, long long ldd,
+                            const double* dmean, const double* dVp, msm_idx_t k, double* outd, int* dflag, const ProjTile* tiles)
+{
+    if (dtype_bytes == 2) proj_mfma_blocks<Bf16Raw>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
+    else if (dtype_bytes == 4) proj_mfma_blocks<float>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
+    else proj_mfma_blocks<double>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
+    MSM_HIP_CHECK(hipGetLastError());
+    return MSM_OK;
+}
+
 static int proj_upload(ProjParams& Q, const double* mean, const double* comps, msm_idx_t k, msm_idx_t n_features)
 {
     DevBuf &dPar = pool(PS_PAR), &dVp = pool(PS_W);
@@ -1767,16 +1777,7 @@ static int proj_upload(ProjParams& Q, const double* mean, const double* comps, m
     const msm_idx_t nkb = ceil_div(k, 16);
     if ((rc = dPar.reserve(par_n * sizeof(double) + 16))) return rc;
     if ((rc = dVp.reserve((size_t)nkb * n_features * 16 * sizeof(double)))) return rc;
-    Q.muV.assign((size_t)k, 0.0);
-    for (msm_idx_t c = 0; c < k; ++c) {
-        double sacc = 0.0;
-        for (msm_idx_t f = 0; f < n_features; ++f) sacc += mean[f] * comps[c * n_features + f];
-        Q.muV[(size_t)c] = sacc;
-    }
-    Q.vp.assign((size_t)nkb * n_features * 16, 0.0);   // components in blocks of 16, panel Vp[F][16] (feature-major, zero padded)
-    for (msm_idx_t c = 0; c < k; ++c)
-        for (msm_idx_t f = 0; f < n_features; ++f)
-            Q.vp[((size_t)(c / 16) * n_features + f) * 16 + (c % 16)] = comps[c * n_features + f];
+    proj_host_params(mean, comps, k, n_features, Q.muV, Q.vp);
     Q.dmean = dPar.as<double>();
     Q.dcomps = Q.dmean + k;
     Q.dflag = reinterpret_cast<int*>(Q.dcomps + (size_t)k * n_features);
@@ -1795,28 +1796,8 @@ static int proj_launch(const ProjParams& Q, const void* Xd, int dtype_bytes, msm
     const unsigned grid = (unsigned)ceil_div(n_rows, 128);
     const int cw = 16 / dtype_bytes;
     const int vec = (((uintptr_t)Xd) % 16 == 0) && (ldd % cw == 0) && (n_features % cw == 0);
-    if (vec && (size_t)256 * ldd * dtype_bytes < ((size_t)1 << 32)) {
-        // fp64-MFMA path
-        const msm_idx_t nkb = ceil_div(k, 16);
-        const unsigned g2 = (unsigned)ceil_div(n_rows, 256);
-        for (msm_idx_t kb = 0; kb < nkb; ++kb) {
-            const int kk = (int)std::min<msm_idx_t>(16, k - kb * 16);
-            const double* vpk = Q.dVp + (size_t)kb * n_features * 16;
-            if (dtype_bytes == 2)
-                hipLaunchKernelGGL((tica_project_mfma_kernel<Bf16Raw>), dim3(g2), dim3(NT), 0, stream(), (const Bf16Raw*)Xd,
-                                   (long long)n_rows, (int)n_features, (long long)ldd, Q.dmean, vpk, kk, (int)(kb * 16), (int)k,
-                                   outd, Q.dflag, nullptr);
-            else if (dtype_bytes == 4)
-                hipLaunchKernelGGL((tica_project_mfma_kernel<float>), dim3(g2), dim3(NT), 0, stream(), (const float*)Xd,
-                                   (long long)n_rows, (int)n_features, (long long)ldd, Q.dmean, vpk, kk, (int)(kb * 16), (int)k,
-                                   outd, Q.dflag, nullptr);
-            else
-                hipLaunchKernelGGL((tica_project_mfma_kernel<double>), dim3(g2), dim3(NT), 0, stream(), (const double*)Xd,
-                                   (long long)n_rows, (int)n_features, (long long)ldd, Q.dmean, vpk, kk, (int)(kb * 16), (int)k,
-                                   outd, Q.dflag, nullptr);
-        }
-        MSM_HIP_CHECK(hipGetLastError());
-        return MSM_OK;
+    if (vec && (size_t)256 * ldd * dtype_bytes < ((size_t)1 << 32)) {   // fp64-MFMA path
+        return proj_launch_mfma(dtype_bytes, (unsigned)ceil_div(n_rows, 256), Xd, n_rows, n_features, ldd, Q.dmean, Q.dVp, k, outd, Q.dflag, nullptr);
     }
     const int npw = (int)std::min<msm_idx_t>(8, ceil_div(k, 4));  // components per wave
     double* dmean = Q.dmean;
@@ -1848,6 +1829,8 @@ static int proj_launch(const ProjParams& Q, const void* Xd, int dtype_bytes, msm
     MSM_HIP_CHECK(hipGetLastError());
     return MSM_OK;
 }
+
+extern "C" {
 
 int msm_tica_project(const void* X, int dtype_bytes, msm_idx_t n_rows, msm_idx_t n_features,
                      msm_idx_t ld, const double* mean, const double* comps, msm_idx_t k,
@@ -2020,37 +2003,17 @@ int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, c
     if ((rc = dPar.reserve((size_t)k * sizeof(double) + 16))) return rc;
     if ((rc = dVp.reserve((size_t)nkb * n_features * 16 * sizeof(double)))) return rc;
     if ((rc = dT.reserve(tiles.size() * sizeof(ProjTile)))) return rc;
-    std::vector<double> muV((size_t)k), vp((size_t)nkb * n_features * 16, 0.0);
-    for (msm_idx_t c = 0; c < k; ++c) {
-        double sacc = 0.0;
-        for (msm_idx_t f = 0; f < n_features; ++f) {
-            sacc += mean[f] * comps[c * n_features + f];
-            vp[((size_t)(c / 16) * n_features + f) * 16 + (c % 16)] = comps[c * n_features + f];
-        }
-        muV[(size_t)c] = sacc;
-    }
+    std::vector<double> muV, vp;
+    proj_host_params(mean, comps, k, n_features, muV, vp);
     double* dmean = dPar.as<double>();
     int* dflag = reinterpret_cast<int*>(dmean + k);
     MSM_HIP_CHECK(hipMemcpyAsync(dmean, muV.data(), k * sizeof(double), hipMemcpyHostToDevice, stream()));
     MSM_HIP_CHECK(hipMemsetAsync(dflag, 0, sizeof(int), stream()));
     MSM_HIP_CHECK(hipMemcpyAsync(dVp.p, vp.data(), vp.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
     MSM_HIP_CHECK(hipMemcpyAsync(dT.p, tiles.data(), tiles.size() * sizeof(ProjTile), hipMemcpyHostToDevice, stream()));
-    const ProjTile* dtiles = dT.as<ProjTile>();
-    const unsigned g2 = (unsigned)tiles.size();
-    for (msm_idx_t kb = 0; kb < nkb; ++kb) {
-        const int kk = (int)std::min<msm_idx_t>(16, k - kb * 16);
-        const double* vpk = dVp.as<double>() + (size_t)kb * n_features * 16;
-        if (dtype_bytes == 2)
-            hipLaunchKernelGGL((tica_project_mfma_kernel<Bf16Raw>), dim3(g2), dim3(NT), 0, stream(), (const Bf16Raw*)nullptr, 0LL,
-                               (int)n_features, (long long)n_features, dmean, vpk, kk, (int)(kb * 16), (int)k, (double*)nullptr, dflag, dtiles);
-        else if (dtype_bytes == 4)
-            hipLaunchKernelGGL((tica_project_mfma_kernel<float>), dim3(g2), dim3(NT), 0, stream(), (const float*)nullptr, 0LL,
-                               (int)n_features, (long long)n_features, dmean, vpk, kk, (int)(kb * 16), (int)k, (double*)nullptr, dflag, dtiles);
-        else
-            hipLaunchKernelGGL((tica_project_mfma_kernel<double>), dim3(g2), dim3(NT), 0, stream(), (const double*)nullptr, 0LL,
-                               (int)n_features, (long long)n_features, dmean, vpk, kk, (int)(kb * 16), (int)k, (double*)nullptr, dflag, dtiles);
-    }
-    MSM_HIP_CHECK(hipGetLastError());
+    if ((rc = proj_launch_mfma(dtype_bytes, (unsigned)tiles.size(), nullptr, 0LL, n_features, (long long)n_features, dmean, dVp.as<double>(), k,
+                               nullptr, dflag, dT.as<ProjTile>())))
+        return rc;
     int f2 = 0;
     if (check_finite) MSM_HIP_CHECK(hipMemcpyAsync(&f2, dflag, sizeof(int), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `tiles`, `vp` and `muV` die with this frame

@@ -11,6 +11,7 @@ constexpr int BK32 = 32;    // frames per K-step, fp32 kernel
 constexpr int BK64 = 16;    // frames per K-step, fp64 kernel
 constexpr int KCMAX = 4096; // max frames per chunk (load-balance granule)
 constexpr int KFLUSH = 8192; // max frames accumulated in fp32 registers before an fp64 merge
+constexpr int KFLUSH_SYM = 4096; // sum/difference kernel: frames in fp32 registers between fp64 merges (tica_sym_dev.h)
 constexpr int NCB = 1024;   // column-sum partial slots (4 blocks per CU)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -24,8 +24,6 @@ namespace msm {
 // Used from T = 2 tiles (F > 128) up to the width whose T(T+1)/2 upper tiles still fit one resident round
 // (F <= 3968 on 256 CUs); a single tile has nothing to save (1 H + 1 D against 1 G + 1 C).
 // ---------------------------------------------------------------------------
-constexpr int KFLUSH_SYM = 4096;
-
 __device__ __forceinline__ float4 f4mul(float4 a, float4 m) { return make_float4(a.x * m.x, a.y * m.y, a.z * m.z, a.w * m.w); }
 
 // a - b on four floats as two v_pk_add_f32 with the negate modifiers on the second source (the compiler splits a
