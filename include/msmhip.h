@@ -292,6 +292,20 @@ int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, c
 int msm_tica_project_host_list(const void* const* X_ptrs, const msm_idx_t* n_rows, msm_idx_t n_seq, int dtype_bytes,
                                msm_idx_t n_features, const double* mean, const double* comps, msm_idx_t k, double* out,
                                int check_finite);
+/* Which kernel a projection of rows of n_features elements of dtype_bytes (2 | 4 | 8) at row stride ld launches -- the
+ * library's one dispatch, for tests to ask (pure: works with no device visible).  With cw = 16 / dtype_bytes elements per
+ * 16-byte vector, rows are read with vector loads (*vec = 1) when the base pointer is 16-byte aligned (aligned16) and both
+ * n_features and ld are multiples of cw, element by element (*vec = 0) otherwise.  Vector rows take the fp64-MFMA kernel
+ * (MSM_PJ_MFMA) while 256 * ld * dtype_bytes < 2^32 -- its row offsets inside a 256-row tile are 32-bit -- and the
+ * lane-per-row kernel (MSM_PJ_ROWS) from that stride on; rows without vector loads always take MSM_PJ_ROWS.
+ * msm_tica_project_batch admits exactly the widths for which (n_features, ld = n_features, aligned16 = 1) is MSM_PJ_MFMA. */
+enum { MSM_PJ_MFMA = 0, MSM_PJ_ROWS = 1 };
+int msm_tica_project_plan(int dtype_bytes, msm_idx_t n_features, msm_idx_t ld, int aligned16, int* kernel, int* vec);
+/* What the last projection calls of this process did: out2 = {groups the last msm_tica_project_host_list call staged its rows
+ * in, 256-row tiles of the last msm_tica_project_batch call}; 0 for a call that had no rows or was refused.  The host list's
+ * groups hold MSM_TICA_PROJ_GROUP_BYTES bytes of rows (read per call; unset or not positive: 512 MiB): whole trajectories in
+ * order, a new group where the next trajectory would pass the budget of a group that already holds rows. */
+int msm_tica_project_last_stats(msm_idx_t* out2);
 
 /* ---- libdistance: exact-arithmetic vector metrics --------------------- */
 /* metric in {"euclidean","sqeuclidean","cityblock","chebyshev","canberra",

@@ -27,6 +27,9 @@ TICA_F64 = 1
 TICA_BF16 = 2
 TICA_BF16X2 = 3
 
+MSM_PJ_MFMA = 0   # msm_tica_project_plan: the fp64-MFMA projection kernel / the lane-per-row one
+MSM_PJ_ROWS = 1
+
 _i64 = C.c_int64
 _p = C.c_void_p
 _i64p = C.POINTER(C.c_int64)
@@ -90,6 +93,8 @@ def _declare(lib):
     f("msm_tica_project", C.c_int, _p, C.c_int, _i64, _i64, _i64, _p, _p, _i64, _p, C.c_int, C.c_int)
     f("msm_tica_project_batch", C.c_int, C.POINTER(_p), C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _p, _p, _i64, C.c_int)
     f("msm_tica_project_host_list", C.c_int, C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _p, _p, _i64, _p, C.c_int)
+    f("msm_tica_project_plan", C.c_int, C.c_int, _i64, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int))
+    f("msm_tica_project_last_stats", C.c_int, _i64p)
     f("msm_tica_last_folded", C.c_int, _p, C.POINTER(C.c_int))
     f("msm_tica_last_img_fused", C.c_int, _p, C.POINTER(C.c_int))
     f("msm_tica_last_img_carried", C.c_int, _p, C.POINTER(C.c_int))

@@ -1789,14 +1789,31 @@ static int proj_upload(ProjParams& Q, const double* mean, const double* comps, m
     return MSM_OK;
 }
 
+// Which projection kernel rows of n_features elements at row stride ld take, decided in ONE place (exported to the tests as
+// msm_tica_project_plan; pure).  Rows that are whole 16-byte vectors at 16-byte aligned addresses are read with vector
+// loads; they go to the fp64-MFMA kernel while a 256-row tile spans less than 2^32 bytes (its row offsets are 32-bit), to the
+// lane-per-row kernel with vector loads beyond, and every other row to the lane-per-row kernel element by element.
+struct ProjPlan {
+    int kernel, vec;
+};
+static ProjPlan proj_plan(int dtype_bytes, msm_idx_t n_features, msm_idx_t ld, bool aligned16)
+{
+    const int cw = 16 / dtype_bytes;
+    const int vec = aligned16 && (ld % cw == 0) && (n_features % cw == 0);
+    const bool mfma = vec && (size_t)256 * ld * dtype_bytes < ((size_t)1 << 32);
+    return ProjPlan{mfma ? MSM_PJ_MFMA : MSM_PJ_ROWS, vec};
+}
+
+static long long g_pj_stats[2] = {0, 0};   // groups of the last host-list call, tiles of the last batch call
+
 // out[n_rows][k] (device) = (X - mean) comps^T for the device-resident X[n_rows][ldd]; queued on stream(), nothing synchronised
 static int proj_launch(const ProjParams& Q, const void* Xd, int dtype_bytes, msm_idx_t n_rows, msm_idx_t n_features, msm_idx_t ldd,
                        msm_idx_t k, double* outd)
 {
     const unsigned grid = (unsigned)ceil_div(n_rows, 128);
-    const int cw = 16 / dtype_bytes;
-    const int vec = (((uintptr_t)Xd) % 16 == 0) && (ldd % cw == 0) && (n_features % cw == 0);
-    if (vec && (size_t)256 * ldd * dtype_bytes < ((size_t)1 << 32)) {   // fp64-MFMA path
+    const ProjPlan pl = proj_plan(dtype_bytes, n_features, ldd, ((uintptr_t)Xd) % 16 == 0);
+    const int vec = pl.vec;
+    if (pl.kernel == MSM_PJ_MFMA) {
         return proj_launch_mfma(dtype_bytes, (unsigned)ceil_div(n_rows, 256), Xd, n_rows, n_features, ldd, Q.dmean, Q.dVp, k, outd, Q.dflag, nullptr);
     }
     const int npw = (int)std::min<msm_idx_t>(8, ceil_div(k, 4));  // components per wave
@@ -1892,9 +1909,14 @@ int msm_tica_project_host_list(const void* const* X_ptrs, const msm_idx_t* n_row
         if (n_rows[s] < 0 || (n_rows[s] > 0 && !X_ptrs[s])) return fail(MSM_ERR_INVALID, "bad sequence %lld", (long long)s);
         total += (size_t)n_rows[s];
     }
+    g_pj_stats[0] = 0;
     if (total == 0) return MSM_OK;
     const size_t row_bytes = (size_t)n_features * dtype_bytes;
-    const size_t budget = (size_t)512 << 20;
+    size_t budget = (size_t)512 << 20;
+    if (const char* be = getenv("MSM_TICA_PROJ_GROUP_BYTES")) {   // bytes per group (the tests' group seams at small sizes); read per call
+        const long long b = atoll(be);
+        if (b > 0) budget = (size_t)b;
+    }
     // groups of whole trajectories, rows packed back to back (a trajectory larger than the budget is a group of its own)
     std::vector<msm_idx_t> gend;
     size_t half = 0;
@@ -1913,6 +1935,7 @@ int msm_tica_project_host_list(const void* const* X_ptrs, const msm_idx_t* n_row
         half = std::max(half, bytes);
     }
     half = (half + 255) & ~(size_t)255;
+    g_pj_stats[0] = (long long)gend.size();
     DevBuf &dX = pool(PS_X), &dOut = pool(PS_OUT);
     int rc;
     if ((rc = dX.reserve(2 * half))) return rc;
@@ -1979,8 +2002,8 @@ int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, c
         return fail(MSM_ERR_INVALID, "dtype_bytes must be 2 (bfloat16), 4 or 8");
     if (n_seq < 0 || n_features < 1 || k < 1) return fail(MSM_ERR_INVALID, "bad shape");
     if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
-    const int cw = 16 / dtype_bytes;
-    if (n_features % cw != 0 || (size_t)256 * n_features * dtype_bytes >= ((size_t)1 << 32))
+    g_pj_stats[1] = 0;
+    if (proj_plan(dtype_bytes, n_features, n_features, true).kernel != MSM_PJ_MFMA)   // whole 16-byte vectors, 32-bit tile offsets
         return fail(MSM_ERR_INVALID, "msm_tica_project_batch: rows must be whole 16-byte vectors");
     std::vector<ProjTile> tiles;
     for (msm_idx_t s = 0; s < n_seq; ++s) {
@@ -1996,6 +2019,7 @@ int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, c
             tiles.push_back(t);
         }
     }
+    g_pj_stats[1] = (long long)tiles.size();
     if (tiles.empty()) return MSM_OK;
     int rc;
     DevBuf &dPar = pool(PS_PAR), &dVp = pool(PS_W), &dT = pool(PS_IDX);
@@ -2018,6 +2042,23 @@ int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, c
     if (check_finite) MSM_HIP_CHECK(hipMemcpyAsync(&f2, dflag, sizeof(int), hipMemcpyDeviceToHost, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `tiles`, `vp` and `muV` die with this frame
     if (check_finite && f2) return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
+    return MSM_OK;
+}
+
+int msm_tica_project_plan(int dtype_bytes, msm_idx_t n_features, msm_idx_t ld, int aligned16, int* kernel, int* vec)
+{
+    if ((dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8) || n_features < 1 || ld < n_features || !kernel || !vec)
+        return fail(MSM_ERR_INVALID, "msm_tica_project_plan: bad argument");
+    const ProjPlan pl = proj_plan(dtype_bytes, n_features, ld, aligned16 != 0);
+    *kernel = pl.kernel;
+    *vec = pl.vec;
+    return MSM_OK;
+}
+
+int msm_tica_project_last_stats(msm_idx_t* out2)
+{
+    if (!out2) return fail(MSM_ERR_INVALID, "msm_tica_project_last_stats: null pointer");
+    for (int i = 0; i < 2; ++i) out2[i] = g_pj_stats[i];
     return MSM_OK;
 }
 
