@@ -530,6 +530,31 @@ int msm_landmark_predict_f64(const double* X, msm_idx_t n, msm_idx_t m, const do
                              const char* pooling, msm_idx_t* labels, double* pooled, int* negative, int on_device);
 int msm_landmark_predict_plan(msm_idx_t m, int elem_size, msm_idx_t* out4);
 
+/* ---- Nystroem kernel feature map (decomposition/kernel_approximation.py, ktica.py) ------------------------------------
+ * out[i, :] = k(rows[i], landmarks) . B - c     (rows: n x n_features at row stride ld elements; landmarks: L x
+ * n_features of the rows' dtype; B: L x P float64; c: P float64 or NULL; landmarks, B and c are HOST arrays).
+ *   kernel: enum msm_kernel below.  gamma arrives resolved (the estimators turn None into 1 / n_features); coef0 and degree
+ *   are read by poly and sigmoid only.  cosine divides by the norms the way scikit-learn's normalize does (a zero vector is
+ *   left as it is: its kernel values are 0).
+ *   out (n x P) has the rows' dtype, or float64 when out_f64 is set; rows and out follow on_device (host rows are staged in
+ *   groups; pitched host rows are compacted by the copy).  The call runs on the stream of msm_set_stream and synchronises it.
+ *   Arithmetic: float64 for both row dtypes (float32 rows are widened exactly); the result is rounded once.
+ *   Routes: while 16 rows x L kernel values fit the LDS budget one fused launch keeps them in LDS; above, two launches per
+ *   chunk of scratch_rows rows (0: the plan's default) go through a library-owned buffer.  MSM_NYSTROEM_FUSED=0 forces the
+ *   second route; both accumulate every output element in the same order and are bit-identical.
+ * MSM_ERR_NONFINITE ("Input contains NaN, infinity or a value too large") when a row or landmark value is not finite;
+ * MSM_ERR_INVALID for an unknown kernel id, null pointers and bad shapes.  n = 0 succeeds without a device.
+ * msm_kernel_map_plan: out9 = {1 fused / 0 scratch, rows per workgroup R, landmark tile, feature depth per MFMA, tile of B's
+ *   columns, L padded to the tile, pitch of the block in doubles, LDS bytes of the block, default rows per scratch chunk}. */
+enum msm_kernel { MSM_K_LINEAR = 0, MSM_K_POLY = 1, MSM_K_SIGMOID = 2, MSM_K_COSINE = 3, MSM_K_RBF = 4, MSM_K_LAPLACIAN = 5 };
+int msm_kernel_map_f32(const float* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, const float* landmarks, msm_idx_t L,
+                       const double* B, msm_idx_t P, const double* c, int kernel, double gamma, double coef0, double degree,
+                       void* out, int out_f64, int on_device, msm_idx_t scratch_rows);
+int msm_kernel_map_f64(const double* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, const double* landmarks, msm_idx_t L,
+                       const double* B, msm_idx_t P, const double* c, int kernel, double gamma, double coef0, double degree,
+                       void* out, int out_f64, int on_device, msm_idx_t scratch_rows);
+int msm_kernel_map_plan(msm_idx_t L, msm_idx_t P, msm_idx_t n_features, int itemsize, msm_idx_t* out9);
+
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works
  * in the type of X -- float32 rows give float32 centres / counts, everything else is float64 -- and the reference

@@ -1,4 +1,6 @@
 """Decompositions of the MSMBuilder hot path on MI355X (reference: msmbuilder/decomposition)."""
 from .tica import tICA
+from .kernel_approximation import Nystroem, LandmarkNystroem
+from .ktica import KernelTICA
 
-__all__ = ['tICA']
+__all__ = ['tICA', 'KernelTICA', 'Nystroem', 'LandmarkNystroem']
