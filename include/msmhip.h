@@ -555,6 +555,54 @@ int msm_kernel_map_f64(const double* rows, msm_idx_t n, msm_idx_t n_features, ms
                        void* out, int out_f64, int on_device, msm_idx_t scratch_rows);
 int msm_kernel_map_plan(msm_idx_t L, msm_idx_t P, msm_idx_t n_features, int itemsize, msm_idx_t* out9);
 
+/* ---- Gaussian hidden Markov model: the E-step (hmm/gaussian.py) ----------------------------------------------------------
+ * rows: n x n_features at row stride ld elements, the trajectories back to back; offsets: n_traj + 1 HOST row offsets
+ * (offsets[0] = 0, offsets[n_traj] = n, no empty trajectory).  means, vars: n_states x n_features; transmat: n_states x
+ * n_states (clamped at 1e-20 as HMMFitter::set_transmat does); log_startprob: n_states, ADDED to the first frame's log
+ * likelihoods as HMMFitter does with its log_startprob (the reference's estimator hands it 1 / n_states, not the logarithm;
+ * the estimator here does the same).  All parameters and all outputs but loglik's are HOST float64 arrays; rows follow
+ * on_device (host rows are staged, pitched ones compacted by the copy).  Arithmetic: float64 for both row dtypes.  The
+ * emission term is -0.5 (F c + sum_f (x - mu)^2 / var + log var) with c = log(2 pi) rounded to float as the reference has it.
+ *   msm_hmm_estep:   traj_logprob (n_traj), post (K), obs and obs2 (K x F), trans (K x K) and *logprob, the sum of
+ *                    traj_logprob in trajectory order.  Forward-backward runs parallel in time over segments of `segment`
+ *                    frames (0: the plan's default; at most the plan's S_max): operators per segment, a stitch per
+ *                    trajectory, a fused pass per segment, an ordered reduction of at most 1024 partials.  Neither emissions
+ *                    nor lattices nor posteriors reach device memory; no atomics: the same call gives the same bits.  A state
+ *                    whose emission weight in a frame is below the smallest normal double relative to the frame's largest is
+ *                    dropped from that frame.
+ *   msm_hmm_score:   the forward half (operators and stitch): the same traj_logprob and *logprob, bit for bit, for the same
+ *                    segment.  It keeps nothing per frame, so any segment is served: one as long as the longest trajectory
+ *                    is the forward recursion serial in time, one workgroup per trajectory.
+ *   msm_hmm_loglik:  out (n x n_states float64, follows on_device) = the emission log-likelihoods.
+ *   msm_hmm_viterbi: the reference's log-space recursion, one wave per trajectory, sequential in time, first maximum in the
+ *                    induction, at the last frame and in the traceback; states (n, HOST int), traj_logprob (n_traj), *logprob.
+ *                    One back-pointer byte per (frame, state) in a library-owned buffer.
+ *   msm_hmm_plan:    out8 = {default segment S, S_max (the longest whose alpha block fits LDS), largest n_states served,
+ *                    threads of a workgroup (one owns ceil(K^2 / threads) matrix entries), frames of an emission chunk in the
+ *                    operator pass, partials of the fused pass at most, frames of a Viterbi chunk, LDS bytes of the fused pass
+ *                    at the default S}.
+ * MSM_ERR_INVALID: n_states above the served limit (the message names it), non-positive or non-finite variances, n = 0 or
+ * no / an empty trajectory ("sequences is empty"), segment above S_max, null pointers, bad shapes.  MSM_ERR_NONFINITE
+ * ("Input contains NaN, infinity or a value too large") when a row element is not finite. */
+#define MSM_HMM_DECL(SFX, T)                                                                                                       \
+    int msm_hmm_estep_##SFX(const T* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, const msm_idx_t* offsets,               \
+                            msm_idx_t n_traj, msm_idx_t n_states, const double* means, const double* vars, const double* transmat, \
+                            const double* log_startprob, msm_idx_t segment, double* traj_logprob, double* post, double* obs,       \
+                            double* obs2, double* trans, double* logprob, int on_device);                                          \
+    int msm_hmm_score_##SFX(const T* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, const msm_idx_t* offsets,               \
+                            msm_idx_t n_traj, msm_idx_t n_states, const double* means, const double* vars, const double* transmat, \
+                            const double* log_startprob, msm_idx_t segment, double* traj_logprob, double* logprob, int on_device); \
+    int msm_hmm_loglik_##SFX(const T* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, msm_idx_t n_states,                   \
+                             const double* means, const double* vars, double* out, int on_device);                                 \
+    int msm_hmm_viterbi_##SFX(const T* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, const msm_idx_t* offsets,             \
+                              msm_idx_t n_traj, msm_idx_t n_states, const double* means, const double* vars,                      \
+                              const double* transmat, const double* log_startprob, int* states, double* traj_logprob,             \
+                              double* logprob, int on_device);
+MSM_HMM_DECL(f32, float)
+MSM_HMM_DECL(f64, double)
+#undef MSM_HMM_DECL
+int msm_hmm_plan(msm_idx_t n_states, msm_idx_t n_features, int itemsize, msm_idx_t* out8);
+
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works
  * in the type of X -- float32 rows give float32 centres / counts, everything else is float64 -- and the reference

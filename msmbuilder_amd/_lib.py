@@ -141,6 +141,13 @@ def _declare(lib):
     for sfx in ("f32", "f64"):
         f("msm_kernel_map_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, C.c_int, C.c_double, C.c_double,
           C.c_double, _p, C.c_int, C.c_int, _i64)
+    f("msm_hmm_plan", C.c_int, _i64, _i64, C.c_int, _i64p)
+    for sfx in ("f32", "f64"):
+        f("msm_hmm_estep_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _f64p,
+          C.c_int)
+        f("msm_hmm_score_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _f64p, C.c_int)
+        f("msm_hmm_loglik_" + sfx, C.c_int, _p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int)
+        f("msm_hmm_viterbi_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _f64p, C.c_int)
     f("msm_tica_export_sums", C.c_int, _p, _p, _p)
     f("msm_tica_reduce", C.c_int, _p, C.c_double, _i64, _p, _p, _p, _p)
     f("msm_tica_backsolve", C.c_int, _p, _p, _i64, _p)
