@@ -7,7 +7,15 @@ choice of labels and each iteration's centres are a function of its labels alone
     inertia   against the float64 sum at the device's own centres and labels in the inertia kernel's arithmetic
               (difference in T, square and sum in float64), n 2^-53 relative
 
-Seam sizes (piece length, rows per histogram wave, features per tile) come from msm_lloyd_plan.
+Seam sizes (piece length, rows per histogram wave, features per tile) come from msm_lloyd_plan.  Beyond those, the cases of
+``trajectory_cases`` hold: the label chunk of the histogram and scatter waves (K = 2048, 2049, 4097: one, two and three
+chunks, with empty clusters in two of them); the base kernel's chunk of 256 clusters (K = 255, 256, 257, empty clusters on
+both sides of cluster 256); a relocation at an odd and at an even iteration after the first, twice in one run, and in the last
+permitted iteration (``late_*``); a donor that loses two rows in one update and a donor that loses its only row, keeps its
+centre and is empty again (``donor_*``, small integers: the centres must come out exact).  A donor's device sum holds the
+rows that left it, so its centre bound counts them (``center_bound``'s ``taken``, from the reference's own relocation).
+test_rows_one_element_into_their_allocation runs the update on rows that are not 16-byte aligned (the per-element loads of
+the segmented sum); test_default_init_equals_scikit_learn_live holds the estimator's default init to scikit-learn itself.
 """
 import os
 
@@ -38,16 +46,20 @@ def _reference(name, X, init, max_iter, tol_abs, argmin=None):
     return _REF[name]
 
 
-def _check_against_reference(name, X, init, max_iter, tol_abs, argmin=None):
+def _check_against_reference(name, X, init, max_iter, tol_abs, argmin=None, rows=None):
+    """``rows``: what is handed to lloyd_run in place of the host array X (a device tensor with X's values)."""
     ref = _reference(name, X, init, max_iter, tol_abs, argmin)
-    centers, labels, inertia, n_iter, status = lloyd_run(X, init, max_iter, tol_abs)
+    centers, labels, inertia, n_iter, status = lloyd_run(X if rows is None else rows, init, max_iter, tol_abs)
+    if rows is not None:
+        labels = labels.cpu().numpy()
     print(name, "n_iter", n_iter, ref["n_iter"], "status", LR.STATUS_OF[status], ref["status"], "inertia", inertia)
     assert n_iter == ref["n_iter"]
     assert LR.STATUS_OF[status] == ref["status"]
     assert labels.dtype == np.int32 and np.array_equal(labels, ref["labels"])
     assert centers.dtype == X.dtype
     err = np.abs(centers.astype(np.float64) - ref["centers"].astype(np.float64))
-    bound = LR.center_bound(X, ref["summed"], ref["centers"])    # (the members the last update summed)
+    # (the members the last update summed, and the rows its relocation took out of a donor's sum again)
+    bound = LR.center_bound(X, ref["summed"], ref["centers"], taken=ref["taken"])
     print(name, "max centre error / bound", float(np.max(err / np.maximum(bound, 1e-300))))
     assert np.all(err <= bound)
     want = LR.kernel_inertia(X, centers, labels)
@@ -67,6 +79,37 @@ def test_trajectory_equals_the_reference_loop(name):
     if name.startswith("reloc_"):
         assert len(ref["relocated"][0]) >= 1
         assert np.bincount(labels, minlength=init.shape[0]).min() >= 1
+    if name in LR.LATE:
+        assert [i for i, r in enumerate(ref["relocated"]) if r] == LR.LATE[name][3]
+        if "_last_" in name:                                 # the relocation closes the run: labels against the FINAL centres
+            assert ref["status"] == LR.MAXITER and np.array_equal(labels, R.exact_argmin(X, centers)[0])
+    if name in LR.DONOR:                                     # small integers: every sum is exact, so is every centre
+        assert (ref["n_iter"], ref["status"]) == LR.DONOR[name][1:3]
+        assert np.array_equal(centers, ref["centers"])
+    if name.startswith("donor_single_cut"):                  # the donor that lost its only row keeps its centre
+        assert ref["counts"][1] == 0 and np.array_equal(centers[1], init[1])
+
+
+@pytest.mark.parametrize("name", LR.UNALIGNED)
+def test_rows_one_element_into_their_allocation(name):
+    """Contiguous device rows that are a whole number of 16-byte units long but start one element into their allocation:
+    the update must read them by the element (``lloyd_segsum_kernel<T, false>``, units = m), and the run is held to the same
+    reference as the aligned run of the same input.  (Not to the aligned run's bits: the lane partition of the sum differs.)"""
+    import torch
+    X, init, max_iter, tol_abs = CASES[name]
+    n, m = X.shape
+    buf = torch.empty(n * m + 1, dtype=torch.from_numpy(X).dtype, device="cuda")
+    view = buf[1:].view(n, m)
+    view.copy_(torch.from_numpy(X))
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 != 0 and view.is_contiguous()
+    assert (m * X.dtype.itemsize) % 16 == 0
+    assert lloyd_plan(n, m, init.shape[0], X.dtype, aligned=True)["vec16"] == 1
+    plan = lloyd_plan(n, m, init.shape[0], X.dtype, aligned=False)
+    assert plan["vec16"] == 0 and plan["tile_features"] * plan["feature_tiles"] >= m
+    if name == "offset_f32_m512":
+        assert plan["feature_tiles"] == 4
+    _check_against_reference(name, X, init, max_iter, tol_abs, rows=view)
+    assert torch.equal(view.cpu(), torch.from_numpy(X))    # the rows are read, never written
 
 
 def test_at_size_2m_rows():
@@ -165,6 +208,25 @@ def test_scikit_learn_golden(name):
     assert np.array_equal(km.labels_[0], z[name + "_labels"])
     want = z[name + "_centers"]
     assert np.all(np.abs(km.cluster_centers_ - want) <= LR.center_bound(X, z[name + "_labels"], want))
+
+
+@pytest.mark.parametrize("name", LR.GOLDEN_NAMES)
+def test_default_init_equals_scikit_learn_live(name):
+    """The estimator's default, k-means++ on the centred rows on the device, against scikit-learn with the same arguments.
+    tests/test_kmeans_lloyd_ref.py shows the trajectory forced once the draws are scikit-learn's."""
+    import torch
+    cluster = pytest.importorskip("sklearn.cluster")
+    X, kw = LR.default_init_inputs(name)
+    sk = cluster.KMeans(algorithm="lloyd", **kw).fit(X)
+    bound = LR.center_bound(X, sk.labels_, sk.cluster_centers_)
+    for rows in (X, torch.from_numpy(X).cuda()):
+        km = KMeans(**kw).fit([rows])
+        labels = km.labels_[0] if rows is X else km.labels_[0].cpu().numpy()
+        err = np.abs(km.cluster_centers_ - sk.cluster_centers_)
+        print(name, type(rows).__name__, "n_iter", km.n_iter_, sk.n_iter_, "max centre error / bound", float(np.max(err / bound)))
+        assert km.n_iter_ == sk.n_iter_
+        assert np.array_equal(labels, sk.labels_)
+        assert np.all(err <= bound)
 
 
 def test_error_cases():
