@@ -603,6 +603,38 @@ MSM_HMM_DECL(f64, double)
 #undef MSM_HMM_DECL
 int msm_hmm_plan(msm_idx_t n_states, msm_idx_t n_features, int itemsize, msm_idx_t* out8);
 
+/* ---- von Mises hidden Markov model: the image of the angles and the linear E-step (hmm/vonmises.py) ---------------------
+ * The von Mises log-emission sum_f kappa cos(x - mu) - sum_f (log 2 pi + log I0(kappa)) is LINEAR in the image
+ * Z = [cos X | sin X] (n x D, D = 2 n_features):  l_t(k) = cst[k] + sum_j Z[t, j] w[k, j]  with
+ * w = [kappa cos mu | kappa sin mu] (n_states x D) and cst[k] = -sum_f (log 2 pi + log I0(kappa_kf)), both formed by the
+ * caller.  The angles never change over a fit, so the image is formed once and every E-step reads it.
+ *   msm_hmm_trig:       rows (n x n_features at stride ld, host or device by on_device; host rows are staged, pitched ones
+ *                       compacted by the copy) -> Z (DEVICE float64, n rows at stride ldz >= 2 n_features):
+ *                       Z[t, f] = cos(x_tf), Z[t, n_features + f] = sin(x_tf); the element is widened exactly and the
+ *                       trigonometry is float64 for both row types.  16 n_features bytes per frame.  A non-finite angle
+ *                       gives NaN in Z and is reported by whichever msm_hmm_lin_* call reads it.
+ *   msm_hmm_lin_estep, msm_hmm_lin_score, msm_hmm_lin_loglik, msm_hmm_lin_viterbi: what the Gaussian entries of the same
+ *                       names do, with the linear emission over Z (DEVICE memory, always; ldz >= D): the same passes,
+ *                       segments, orders of summation and bit-stability, the same offsets / transmat / log_startprob
+ *                       conventions and msm_hmm_plan (S_max depends on n_states only).  obs is n_states x D = gamma^T Z:
+ *                       its left half is the reference's cosobs, its right half sinobs; there is no obs2.  loglik's out is
+ *                       DEVICE memory, n x n_states.
+ * The same status codes, refusals and messages as the Gaussian entries; w and cst must be finite.  MSM_ERR_NONFINITE
+ * ("Input contains NaN, infinity or a value too large") when an element of Z is not finite. */
+int msm_hmm_trig_f32(const float* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, double* Z, msm_idx_t ldz, int on_device);
+int msm_hmm_trig_f64(const double* rows, msm_idx_t n, msm_idx_t n_features, msm_idx_t ld, double* Z, msm_idx_t ldz, int on_device);
+int msm_hmm_lin_estep(const double* Z, msm_idx_t n, msm_idx_t D, msm_idx_t ldz, const msm_idx_t* offsets, msm_idx_t n_traj,
+                      msm_idx_t n_states, const double* w, const double* cst, const double* transmat, const double* log_startprob,
+                      msm_idx_t segment, double* traj_logprob, double* post, double* obs, double* trans, double* logprob);
+int msm_hmm_lin_score(const double* Z, msm_idx_t n, msm_idx_t D, msm_idx_t ldz, const msm_idx_t* offsets, msm_idx_t n_traj,
+                      msm_idx_t n_states, const double* w, const double* cst, const double* transmat, const double* log_startprob,
+                      msm_idx_t segment, double* traj_logprob, double* logprob);
+int msm_hmm_lin_loglik(const double* Z, msm_idx_t n, msm_idx_t D, msm_idx_t ldz, msm_idx_t n_states, const double* w,
+                       const double* cst, double* out);
+int msm_hmm_lin_viterbi(const double* Z, msm_idx_t n, msm_idx_t D, msm_idx_t ldz, const msm_idx_t* offsets, msm_idx_t n_traj,
+                        msm_idx_t n_states, const double* w, const double* cst, const double* transmat, const double* log_startprob,
+                        int* states, double* traj_logprob, double* logprob);
+
 /* ---- k-means labelling / mini-batch step (GEMM form on MFMA) ----
  * Element type: scikit-learn (the arithmetic behind msmbuilder.cluster.MiniBatchKMeans, cluster/__init__.py:67-69) works
  * in the type of X -- float32 rows give float32 centres / counts, everything else is float64 -- and the reference

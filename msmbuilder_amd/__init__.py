@@ -11,5 +11,5 @@ from . import preprocessing  # noqa: F401
 from .cluster import (KCenters, KMeans, KMedoids, LandmarkAgglomerative, MiniBatchKMeans, MiniBatchKMedoids,  # noqa: F401
                       RegularSpatial)
 from .decomposition import KernelTICA, LandmarkNystroem, Nystroem, tICA  # noqa: F401
-from .hmm import GaussianHMM  # noqa: F401
+from .hmm import GaussianHMM, VonMisesHMM  # noqa: F401
 from .msm import MarkovStateModel  # noqa: F401

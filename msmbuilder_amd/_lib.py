@@ -148,6 +148,11 @@ def _declare(lib):
         f("msm_hmm_score_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _f64p, C.c_int)
         f("msm_hmm_loglik_" + sfx, C.c_int, _p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int)
         f("msm_hmm_viterbi_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _f64p, C.c_int)
+        f("msm_hmm_trig_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, C.c_int)
+    f("msm_hmm_lin_estep", C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _f64p)
+    f("msm_hmm_lin_score", C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _f64p)
+    f("msm_hmm_lin_loglik", C.c_int, _p, _i64, _i64, _i64, _i64, _p, _p, _p)
+    f("msm_hmm_lin_viterbi", C.c_int, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _f64p)
     f("msm_tica_export_sums", C.c_int, _p, _p, _p)
     f("msm_tica_reduce", C.c_int, _p, C.c_double, _i64, _p, _p, _p, _p)
     f("msm_tica_backsolve", C.c_int, _p, _p, _i64, _p)

@@ -13,6 +13,13 @@
 //   hmm_reduce_kernel   the partials summed in workgroup order
 // Neither the N x K emissions nor a lattice nor the posteriors reach HBM; nothing is atomic, every sum has one fixed order.
 // All arithmetic is float64; a float32 element is widened exactly.
+//
+// The emission term has two flavours, chosen at compile time (HmmEmission):
+//   HMM_GAUSS    l_t(k) = cst[k] - 1/2 sum_f (x_tf - mu[k, f])^2 iv[k, f]          rows of T, F columns
+//   HMM_LINEAR   l_t(k) = cst[k] + sum_j z_tj w[k, j]                               rows of float64, D columns (F holds D,
+//                                                                                   mu holds w, iv is unused)
+// The linear one serves the von Mises model over the image Z = [cos X | sin X] that hmm_trig_kernel forms once per fit;
+// its fused pass forms gamma^T [1, Z] only (no squares).
 #pragma once
 #include "common.h"
 
@@ -25,6 +32,9 @@ constexpr int HMM_EC = 16;                          // frames whose emissions th
 constexpr int HMM_VC = 64;                          // frames of a Viterbi chunk (emissions ahead, back-pointers behind)
 constexpr int HMM_G = 1024;                         // workgroups of the fused pass at most (= partials to reduce)
 constexpr double HMM_DROP = -708.0;                 // exp() below this is under the smallest normal double: the state is dropped
+constexpr int HMM_TRIG_WAVES = 8;                   // workgroups per CU of the image kernel's grid at most
+
+enum HmmEmission { HMM_GAUSS = 0, HMM_LINEAR = 1 };
 
 struct HmmArgs {
     const void* X;               // rows, N x F at stride ld elements
@@ -34,9 +44,9 @@ struct HmmArgs {
     long long n_traj, n_seg;
     const long long* off;        // n_traj + 1 row offsets
     const long long* seg0;       // n_traj + 1: first segment of every trajectory
-    const double* mu;            // K x F
-    const double* iv;            // K x F, 1 / variance
-    const double* cst;           // K: -0.5 (F log 2pi + sum log variance)
+    const double* mu;            // K x F (linear emission: the weights w, K x D)
+    const double* iv;            // K x F, 1 / variance (linear emission: unused)
+    const double* cst;           // K: -0.5 (F log 2pi + sum log variance) (linear emission: the constant of the state)
     const double* A;             // K x K, clamped at 1e-20
     const double* logA;          // K x K, log of A
     const double* lsp;           // K: what the recursion adds at the first frame (HMMFitter's log_startprob)
@@ -45,7 +55,7 @@ struct HmmArgs {
     double* alpha_in;            // n_seg x K
     double* beta_out;            // n_seg x K (null: forward half only)
     double* traj_lp;             // n_traj
-    double* part;                // G x psz partials: post K, obs K F, obs2 K F, trans K K
+    double* part;                // G x psz partials: post K, obs K F, obs2 K F, trans K K (linear emission: no obs2)
     double* out;                 // psz
     long long psz;
     int G;
@@ -98,16 +108,31 @@ __device__ __forceinline__ double hmm_loglik1(const T* x, const double* mu, cons
     return cst - 0.5 * s;
 }
 
+// The linear emission over a row of the image; a NaN in it (a non-finite angle) raises the flag like a non-finite row.
+__device__ __forceinline__ double hmm_linear1(const double* z, const double* w, int D, double cst, bool* bad)
+{
+    double s = 0.0;
+    for (int j = 0; j < D; ++j) {
+        const double zv = z[j];
+        *bad |= !isfinite(zv);
+        s += zv * w[j];
+    }
+    return cst + s;
+}
+
 // Emissions of nt frames from row x0 on: b[t * K + k] = exp(l - max_k l) (or l itself when LOG), m[t] = max_k l.
 // Every thread of the workgroup calls it; ends on a barrier.
-template <typename T, bool LOG>
+template <typename T, bool LOG, int EM>
 __device__ __forceinline__ void hmm_emis(const HmmArgs& A, const T* x0, int nt, double* b, double* m)
 {
     const int K = A.K, F = A.F;
     for (int idx = threadIdx.x; idx < nt * K; idx += blockDim.x) {
         const int t = idx / K, k = idx - t * K;
         bool bad = false;
-        b[idx] = hmm_loglik1(x0 + (long long)t * A.ld, A.mu + (long long)k * F, A.iv + (long long)k * F, F, A.cst[k], &bad);
+        if constexpr (EM == HMM_LINEAR)
+            b[idx] = hmm_linear1(x0 + (long long)t * A.ld, A.mu + (long long)k * F, F, A.cst[k], &bad);
+        else
+            b[idx] = hmm_loglik1(x0 + (long long)t * A.ld, A.mu + (long long)k * F, A.iv + (long long)k * F, F, A.cst[k], &bad);
         if (bad) *A.flag = 1;
     }
     __syncthreads();
@@ -130,7 +155,7 @@ __device__ __forceinline__ void hmm_emis(const HmmArgs& A, const T* x0, int nt, 
 __host__ __device__ inline long long hmm_oper_lds(int K, int KP) { return (long long)K * KP + 2LL * K * K + (long long)HMM_EC * K + HMM_EC + 8; }
 __host__ __device__ inline long long hmm_fused_lds(int K, int KP, int S) { return (long long)K * KP + 2LL * S * K + S + 4LL * K + 8; }
 
-template <typename T>
+template <typename T, int EM = HMM_GAUSS>
 __global__ __launch_bounds__(HMM_T) void hmm_oper_kernel(HmmArgs A)
 {
     extern __shared__ double hmm_sm[];
@@ -160,7 +185,7 @@ __global__ __launch_bounds__(HMM_T) void hmm_oper_kernel(HmmArgs A)
     const T* X = static_cast<const T*>(A.X) + row0 * A.ld;
     for (int c0 = 0; c0 < len; c0 += HMM_EC) {
         const int nt = len - c0 < HMM_EC ? len - c0 : HMM_EC;
-        hmm_emis<T, false>(A, X + (long long)c0 * A.ld, nt, sb, smx);   // (its first barrier also covers sA / cur above)
+        hmm_emis<T, false, EM>(A, X + (long long)c0 * A.ld, nt, sb, smx);   // (its first barrier also covers sA / cur above)
         for (int t = 0; t < nt; ++t) {
             const bool head = first && c0 + t == 0;
             double v[HMM_EPT], mx = 0.0;
@@ -274,7 +299,7 @@ __global__ __launch_bounds__(64) void hmm_stitch_kernel(HmmArgs A)
     }
 }
 
-template <typename T>
+template <typename T, int EM = HMM_GAUSS>
 __global__ __launch_bounds__(HMM_T) void hmm_fused_kernel(HmmArgs A)
 {
     extern __shared__ double hmm_sm[];
@@ -303,7 +328,7 @@ __global__ __launch_bounds__(HMM_T) void hmm_fused_kernel(HmmArgs A)
     double* ppost = part;
     double* pobs = part + K;
     double* pobs2 = pobs + (long long)K * F;
-    double* ptrans = pobs2 + (long long)K * F;
+    double* ptrans = EM == HMM_LINEAR ? pobs2 : pobs2 + (long long)K * F;
     const bool lane = tid < K;
     for (long long g = g0; g < g1; ++g) {
         long long row0;
@@ -316,7 +341,7 @@ __global__ __launch_bounds__(HMM_T) void hmm_fused_kernel(HmmArgs A)
             sae[tid] = A.alpha_in[g * K + tid];
             sbe[tid] = A.beta_out[g * K + tid];
         }
-        hmm_emis<T, false>(A, X, len, sb, sn);
+        hmm_emis<T, false, EM>(A, X, len, sb, sn);
         // alpha through the segment (wave 0 works, the others keep step)
         for (int t = 0; t < len; ++t) {
             if (tid < 64) {
@@ -370,7 +395,8 @@ __global__ __launch_bounds__(HMM_T) void hmm_fused_kernel(HmmArgs A)
             }
             __syncthreads();
         }
-        // gamma^T [1, X, X^2] from the LDS block, added to this workgroup's partial in segment order
+        // gamma^T [1, X, X^2] (linear emission: gamma^T [1, Z]) from the LDS block, added to this workgroup's partial in
+        // segment order
         const bool open = g == g0;
         if (lane) {
             double s = 0.0;
@@ -383,10 +409,10 @@ __global__ __launch_bounds__(HMM_T) void hmm_fused_kernel(HmmArgs A)
             for (int t = 0; t < len; ++t) {
                 const double x = (double)X[(long long)t * A.ld + f], gm = sal[t * K + k];
                 s1 += x * gm;
-                s2 += x * x * gm;
+                if constexpr (EM == HMM_GAUSS) s2 += x * x * gm;
             }
             pobs[e] = open ? s1 : pobs[e] + s1;
-            pobs2[e] = open ? s2 : pobs2[e] + s2;
+            if constexpr (EM == HMM_GAUSS) pobs2[e] = open ? s2 : pobs2[e] + s2;
         }
     }
 #pragma unroll
@@ -403,7 +429,7 @@ __global__ __launch_bounds__(HMM_T) void hmm_reduce_kernel(HmmArgs A)
     A.out[e] = s;
 }
 
-template <typename T>
+template <typename T, int EM = HMM_GAUSS>
 __global__ __launch_bounds__(HMM_T) void hmm_loglik_kernel(HmmArgs A)
 {
     const long long idx = (long long)blockIdx.x * HMM_T + threadIdx.x;
@@ -411,15 +437,18 @@ __global__ __launch_bounds__(HMM_T) void hmm_loglik_kernel(HmmArgs A)
     const long long row = idx / A.K;
     const int k = (int)(idx - row * A.K);
     bool bad = false;
-    A.loglik[idx] = hmm_loglik1(static_cast<const T*>(A.X) + row * A.ld, A.mu + (long long)k * A.F, A.iv + (long long)k * A.F, A.F,
-                                A.cst[k], &bad);
+    if constexpr (EM == HMM_LINEAR)
+        A.loglik[idx] = hmm_linear1(static_cast<const T*>(A.X) + row * A.ld, A.mu + (long long)k * A.F, A.F, A.cst[k], &bad);
+    else
+        A.loglik[idx] = hmm_loglik1(static_cast<const T*>(A.X) + row * A.ld, A.mu + (long long)k * A.F, A.iv + (long long)k * A.F, A.F,
+                                    A.cst[k], &bad);
     if (bad) *A.flag = 1;
 }
 
 // Viterbi in log space, one wave per trajectory, sequential in time; lane = state.  The induction takes the FIRST maximum
 // over the previous state, which is also what the reference's traceback (its own argmax over the same sums) arrives at;
 // the last frame takes the first maximum too.  One back-pointer byte per (frame, state).
-template <typename T>
+template <typename T, int EM = HMM_GAUSS>
 __global__ __launch_bounds__(64) void hmm_viterbi_kernel(HmmArgs A)
 {
     extern __shared__ double hmm_sm[];
@@ -436,7 +465,7 @@ __global__ __launch_bounds__(64) void hmm_viterbi_kernel(HmmArgs A)
     for (long long c0 = 0; c0 < len; c0 += HMM_VC) {
         const int nt = (int)(len - c0 < HMM_VC ? len - c0 : HMM_VC);
         __syncthreads();
-        hmm_emis<T, true>(A, X + c0 * A.ld, nt, se, nullptr);
+        hmm_emis<T, true, EM>(A, X + c0 * A.ld, nt, se, nullptr);
         for (int t = 0; t < nt; ++t) {
             if (c0 + t == 0) {
                 if (on) v = A.lsp[i] + se[i];
@@ -481,6 +510,23 @@ __global__ __launch_bounds__(64) void hmm_viterbi_kernel(HmmArgs A)
                 s = sbp[(t - c0) * K + s];
                 A.states[row0 + t - 1] = s;
             }
+    }
+}
+
+// The image of the angles: Z[t, f] = cos(x_tf), Z[t, F + f] = sin(x_tf), the element widened exactly and the
+// trigonometry in float64.  Elementwise, bound by HBM (itemsize in, 16 bytes out per element); a grid-stride loop.  A
+// non-finite angle gives NaN in Z, which the linear emission's own check reports.
+template <typename T>
+__global__ __launch_bounds__(HMM_T) void hmm_trig_kernel(const T* X, long long ld, long long n, int F, double* Z, long long ldz)
+{
+    const long long total = n * F, step = (long long)gridDim.x * HMM_T;
+    for (long long e = (long long)blockIdx.x * HMM_T + threadIdx.x; e < total; e += step) {
+        const long long t = e / F;
+        const int f = (int)(e - t * F);
+        double s, c;
+        sincos((double)X[t * ld + f], &s, &c);
+        Z[t * ldz + f] = c;
+        Z[t * ldz + F + f] = s;
     }
 }
 

@@ -1,4 +1,5 @@
-"""Hidden Markov models (reference: msmbuilder/hmm): ``GaussianHMM`` with its E-step on the device."""
+"""Hidden Markov models (reference: msmbuilder/hmm): ``GaussianHMM`` and ``VonMisesHMM`` with their E-steps on the device."""
 from .gaussian import GaussianHMM
+from .vonmises import VonMisesHMM
 
-__all__ = ['GaussianHMM']
+__all__ = ['GaussianHMM', 'VonMisesHMM']
