@@ -789,6 +789,38 @@ int msm_col_digit_hist(const void* const* X_ptrs, const msm_idx_t* n_rows, msm_i
                        int64_t* hist);
 
 /* ------------------------------------------------------------------------------------------
+ * Time-series smoothers in front of tICA (msmbuilder.preprocessing.timeseries): one linear recurrence
+ * along the time axis of every column, parallel in time.  X_ptrs[s] -> n_rows[s] x n_features at row stride ld elements,
+ * dtype_bytes 4 or 8, host or device by on_device (host rows are staged, pitched ones compacted by the copy); out_ptrs[s]
+ * -> the same rows at stride ld_out, in the same place.  All arithmetic is float64; the recurrence is scipy's lfilter in
+ * transposed direct form II, y = z[0] + b[0] x, z[k] = (z[k+1] + b[k+1] x) - a[k+1] y, every operation rounded on its own.
+ *   MSM_TS_BUTTERWORTH  b, a (order + 1 each, a[0] = 1) and zi (order) are HOST float64 (scipy's butter and lfilter_zi);
+ *                       order 1 .. 8; width odd, >= 3.  Per column: reflect-pad by width - 1 rows (x[w-1:0:-1], x,
+ *                       x[-1:-w:-1]), then filtfilt's defaults on that signal (odd extension by 3 (order + 1), forward from
+ *                       zi * ext[0], backward from zi * y[last]), both paddings cropped; out has the input's dtype, rounded
+ *                       once.  A column holding a non-finite element comes out all NaN.  alpha, adjust, min_periods unused.
+ *   MSM_TS_EWMA         DataFrame.ewm(alpha=alpha, adjust=adjust, min_periods=min_periods).mean() for finite rows: adjust:
+ *                       sum_i (1-alpha)^i x_{t-i} / sum_i (1-alpha)^i; otherwise y_0 = x_0, y_t = (1-alpha) y_{t-1} +
+ *                       alpha x_t; rows below min_periods - 1 are NaN.  out is float64 whatever dtype_bytes.  order, b, a,
+ *                       zi, width unused.
+ *   MSM_TS_DOUBLE_EWMA  (fwd + bwd) / 2 with bwd the EWMA of the time-reversed rows, not reversed back.
+ * segment: frames of a pass (paddings included) per segment of the time-parallel form -- a local pass per (trajectory,
+ * segment, column) from zi * x[segment start], a stitch per (trajectory, column) with A^segment (formed in long double),
+ * a final pass --; 0, or at least the longest trajectory: one segment per trajectory, the recurrence serial in time.  The
+ * same call gives the same bits; results for different `segment` differ by the reassociation at the seams.
+ * MSM_ERR_INVALID: null pointers, bad shapes, dtype_bytes, kind, order, width, coefficients, alpha outside (0, 1], a
+ * negative segment, a Butterworth trajectory shorter than width or whose padded length is not above 3 (order + 1).
+ * MSM_ERR_NONFINITE ("Input contains NaN, infinity or a value too large"): EWMA kinds, a non-finite element (a flag raised
+ * by the final pass, no pass of its own; out is then unspecified). */
+#define MSM_TS_BUTTERWORTH 0
+#define MSM_TS_EWMA 1
+#define MSM_TS_DOUBLE_EWMA 2
+int msm_ts_filter(const void* const* X_ptrs, void* const* out_ptrs, const msm_idx_t* n_rows, msm_idx_t n_seq, int dtype_bytes,
+                  msm_idx_t n_features, msm_idx_t ld, msm_idx_t ld_out, int on_device, int kind, int order, const double* b,
+                  const double* a, const double* zi, msm_idx_t width, double alpha, int adjust, msm_idx_t min_periods,
+                  msm_idx_t segment);
+
+/* ------------------------------------------------------------------------------------------
  * Post-clustering transition counts.  Replaces the counting loop of
  * msmbuilder.msm._transition_counts (/root/reference/msmbuilder/msm/core.py:487-596) for integer
  * labels: y_ptrs[s] -> n_rows[s] int64 labels (device-resident, e.g. KCenters.labels_, or host).

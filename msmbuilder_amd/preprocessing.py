@@ -30,9 +30,10 @@ from . import _lib
 from ._lib import Arr, check, empty_like_placement, is_device_array
 from .base import BaseEstimator
 from .utils.validation import array2d, check_iter_of_sequences
+from .timeseries import Butterworth, EWMA, DoubleEWMA   # noqa: F401  (preprocessing/timeseries.py upstream)
 
 __all__ = ['StandardScaler', 'MinMaxScaler', 'MaxAbsScaler', 'RobustScaler', 'column_statistics',
-           'column_order_statistics', 'fold_into_tica']
+           'column_order_statistics', 'fold_into_tica', 'Butterworth', 'EWMA', 'DoubleEWMA']
 
 
 def _prepare(X):
