@@ -474,6 +474,45 @@ int msm_kmedoids_fit_f64(const double* X, msm_idx_t n, msm_idx_t m, const char* 
  * path (1: one-workgroup, 0: general), snapshots taken in the last pass}. */
 int msm_kmedoids_last_stats(msm_idx_t* out4);
 
+/* ---- the rmsd metric: minimal RMSD after optimal superposition (libdistance's ninth metric) -------------------------
+ * Conformations are float32 xyz[n_frames][n_atoms][3], C-contiguous.  msm_rmsd_prepare makes one pass over them (host or
+ * device, never modified) and keeps, in device memory owned by the handle: every frame minus its centroid (centroid and
+ * difference in float64, rounded once to float32) as an atom-major, frame-fastest image T[3][n_atoms][n_pad] with the
+ * frames zero-padded to a multiple of 64, and G[n] = the float64 sum of squares of those rounded values.
+ *
+ * ONE definition of the distance of frames x, y (csrc/rmsd_dev.h: rmsd_qcp): M_ab = sum_k x_ka * y_kb as a float32 fmaf
+ * chain over the atoms from atom 0; the characteristic quartic of the 4 x 4 key matrix (Theobald 2005) with float64
+ * coefficients; its largest root lambda by Newton from (G_x + G_y) / 2, at most 50 steps, until |step| < 1e-11 |lambda|
+ * or a zero derivative; msd = max((G_x + G_y - 2 lambda) / n_atoms, 0); the distance is sqrt(msd), float64.  Every
+ * function below returns the same bits for the same ordered pair (x, y).  A frame with a NaN or infinite coordinate has
+ * NaN distances.
+ *
+ * X_indices / pair_indices and the outputs follow on_device (all on the host or all on the device); every index is checked
+ * against the frame count (MSM_ERR_INVALID).  Different atom counts: MSM_ERR_INVALID.  All calls synchronise.
+ *   msm_rmsd_dist            out[i] = d(X[X_indices[i]] or X[i], Y[y_frame])
+ *   msm_rmsd_cdist           out[i][j] = d(XA[i], XB[j]), row-major
+ *   msm_rmsd_pdist           condensed d(X[ix[i]], X[ix[j]]), i < j, at msm_kmedoids_condensed_index(i, j, n)
+ *   msm_rmsd_sumdist         *sum = sum_p d(X[pairs[p][0]], X[pairs[p][1]]), added in a fixed order
+ *   msm_rmsd_assign_nearest  assignments[i] = the first j of strictly smallest d(X[i], Y[j]) below FLT_MAX (0 if none: a NaN
+ *                            never wins), min_dist[i] (optional) that distance or FLT_MAX; *inertia = their sum in a fixed
+ *                            order (no atomics: the same bits every run)
+ *   msm_rmsd_kcenters_fit    kcenters.py:79-102 with every pass queued on the device: distances start at +inf, centre k
+ *                            updates rows of strictly smaller distance, the next centre is the first maximum of distances;
+ *                            ids (host, K), labels / distances (n, follow on_device), *inertia = ordered sum of distances */
+typedef struct msm_rmsd msm_rmsd_t;
+int msm_rmsd_prepare(msm_rmsd_t** h, const float* xyz, msm_idx_t n_frames, msm_idx_t n_atoms, int on_device);
+int msm_rmsd_destroy(msm_rmsd_t* h);
+int msm_rmsd_shape(const msm_rmsd_t* h, msm_idx_t* n_frames, msm_idx_t* n_atoms, msm_idx_t* n_pad);
+int msm_rmsd_dist(const msm_rmsd_t* X, const msm_rmsd_t* Y, msm_idx_t y_frame, const msm_idx_t* X_indices,
+                  msm_idx_t n_X_indices, double* out, int on_device);
+int msm_rmsd_cdist(const msm_rmsd_t* XA, const msm_rmsd_t* XB, double* out, int on_device);
+int msm_rmsd_pdist(const msm_rmsd_t* X, const msm_idx_t* X_indices, msm_idx_t n_X_indices, double* out, int on_device);
+int msm_rmsd_sumdist(const msm_rmsd_t* X, const msm_idx_t* pair_indices, msm_idx_t n_pairs, double* sum, int on_device);
+int msm_rmsd_assign_nearest(const msm_rmsd_t* X, const msm_rmsd_t* Y, const msm_idx_t* X_indices, msm_idx_t n_X_indices,
+                            msm_idx_t* assignments, double* min_dist, double* inertia, int on_device);
+int msm_rmsd_kcenters_fit(const msm_rmsd_t* X, msm_idx_t K, msm_idx_t seed, msm_idx_t* ids, msm_idx_t* labels,
+                          double* distances, double* inertia, int on_device);
+
 /* Landmark agglomerative clustering (cluster/agglomerative.py).
  *
  * msm_linkage: agglomerative linkage of n observations from their condensed float64 distance matrix (entry (i, j), i < j,

@@ -129,6 +129,15 @@ def _declare(lib):
     for sfx in ("f32", "f64"):
         f("msm_kmedoids_fit_" + sfx, C.c_int, _p, _i64, _i64, C.c_char_p, _p, _i64, _i64, _i64, _p, _p, _f64p, _i64p, C.c_int)
     f("msm_kmedoids_last_stats", C.c_int, _i64p)
+    f("msm_rmsd_prepare", C.c_int, C.POINTER(_p), _p, _i64, _i64, C.c_int)
+    f("msm_rmsd_destroy", C.c_int, _p)
+    f("msm_rmsd_shape", C.c_int, _p, _i64p, _i64p, _i64p)
+    f("msm_rmsd_dist", C.c_int, _p, _p, _i64, _p, _i64, _p, C.c_int)
+    f("msm_rmsd_cdist", C.c_int, _p, _p, _p, C.c_int)
+    f("msm_rmsd_pdist", C.c_int, _p, _p, _i64, _p, C.c_int)
+    f("msm_rmsd_sumdist", C.c_int, _p, _p, _i64, _f64p, C.c_int)
+    f("msm_rmsd_assign_nearest", C.c_int, _p, _p, _p, _i64, _p, _p, _f64p, C.c_int)
+    f("msm_rmsd_kcenters_fit", C.c_int, _p, _i64, _i64, _p, _p, _p, _f64p, C.c_int)
     f("msm_linkage", C.c_int, _p, _i64, C.c_char_p, _p, C.c_int)
     f("msm_linkage_plan", C.c_int, _i64p)
     f("msm_landmark_within", C.c_int, _p, _i64, _p, _i64, _p, C.c_int)

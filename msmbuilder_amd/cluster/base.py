@@ -5,7 +5,8 @@ between the two: it joins the trajectories (``torch.cat`` for device-resident on
 ``numpy.concatenate`` for host arrays), lets the wrapped single-array estimator run once, and cuts ``labels_`` back
 into one piece per trajectory with the remembered lengths.  ``predict`` / ``transform`` work trajectory by trajectory (in one launch when the trajectories are views of one
 allocation).
-mdtraj trajectories (RMSD metric) are outside this package's scope.
+Estimators that take the rmsd metric (``_takes_rmsd``: KCenters, KMedoids, MiniBatchKMedoids) accept trajectories of
+conformations, 3-D float32 (n_frames, n_atoms, 3) arrays or objects with such an ``.xyz``; mdtraj is never imported.
 """
 import numpy as np
 
@@ -39,6 +40,17 @@ def _join(sequences):
 
 class MultiSequenceClusterMixin(object):
     _allow_trajectory = False
+    _takes_rmsd = False
+
+    def _sequences(self, sequences):
+        """(sequences, ndim of each): 3-D conformations -- an object with ``.xyz`` standing for that array -- when this
+        estimator takes the rmsd metric, has it, and is given such trajectories; 2-D arrays otherwise, as they come."""
+        from .. import libdistance
+        if self._takes_rmsd and libdistance.is_rmsd(getattr(self, 'metric', None)) and isinstance(sequences, (list, tuple)):
+            seqs = [libdistance.conformations(s) for s in sequences]
+            if len(seqs) and all(s is not None for s in seqs):
+                return seqs, 3
+        return sequences, 2
 
     # ------------------------------------------------------------------ bookkeeping
     def _concat(self, sequences):
@@ -66,7 +78,8 @@ class MultiSequenceClusterMixin(object):
     # ------------------------------------------------------------------ estimator protocol
     def fit(self, sequences, y=None):
         """Cluster the frames of all trajectories; ``labels_`` becomes a list with one integer array each."""
-        check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory)
+        sequences, ndim = self._sequences(sequences)
+        check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory, ndim=ndim)
         super(MultiSequenceClusterMixin, self).fit(self._concat(sequences))
         if hasattr(self, 'labels_'):
             self.labels_ = self._split(self.labels_)
@@ -78,7 +91,8 @@ class MultiSequenceClusterMixin(object):
 
     def predict(self, sequences, y=None):
         """Nearest-centre index for every frame of every trajectory (a list of arrays)."""
-        check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory)
+        sequences, ndim = self._sequences(sequences)
+        check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory, ndim=ndim)
         # trajectories that lie back to back in one allocation (views of a joined array / tensor) are labelled in ONE
         # launch and the labels cut per trajectory: a launch per 10,000-frame trajectory fills a sixth of the GPU
         from .._lib import adjacent_view, cut_rows
@@ -104,7 +118,8 @@ class MultiSequenceClusterMixin(object):
         """``fit``, then the training labels, one array per trajectory."""
         wrapped = super(MultiSequenceClusterMixin, self)
         if hasattr(wrapped, 'fit_predict'):
-            check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory)
+            sequences, ndim = self._sequences(sequences)
+            check_iter_of_sequences(sequences, allow_trajectory=self._allow_trajectory, ndim=ndim)
             labels = wrapped.fit_predict(sequences)
         else:
             labels = self.fit(sequences).predict(sequences)

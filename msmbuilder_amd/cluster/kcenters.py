@@ -47,7 +47,8 @@ class _KCenters(ClusterMixin, TransformerMixin):
         How many centres to pick.
     metric : str (default "euclidean")
         One of libdistance's vector metrics: euclidean, sqeuclidean, cityblock, chebyshev, canberra,
-        braycurtis, hamming, jaccard.  (The reference's "rmsd" needs mdtraj trajectories and is out of scope.)
+        braycurtis, hamming, jaccard -- or "rmsd" for conformations: float32 (n_frames, n_atoms, 3) arrays, torch CUDA
+        tensors or objects with such an ``.xyz``; ``cluster_centers_`` is then a host (n_clusters, n_atoms, 3) array.
     random_state : int, numpy RandomState or None
         Source of the first centre: ``check_random_state(random_state).randint(0, n_samples)``, the same
         draw as the reference's, so equal seeds give equal clusterings.
@@ -69,6 +70,8 @@ class _KCenters(ClusterMixin, TransformerMixin):
         self.random_state = random_state
 
     def fit(self, X, y=None):
+        if libdistance.is_rmsd(self.metric) and libdistance.conformations(X) is not None:
+            return self._fit_rmsd(X)
         X = _as_float(X)
         metric = self.metric.decode() if isinstance(self.metric, bytes) else self.metric
         if metric not in libdistance.VECTOR_METRICS:
@@ -105,6 +108,31 @@ class _KCenters(ClusterMixin, TransformerMixin):
         # np.sum(distances_) as in kcenters.py:101 on the host; on the device the kernel's
         # fp64 tree sum of the same values
         self.inertia_ = np.sum(distances) if not ax.on_device else float(inertia.value)
+        return self
+
+    def _fit_rmsd(self, X):
+        """The same loop on conformations, (n_frames, n_atoms, 3) float32: the frames are prepared once, then
+        ``msm_rmsd_kcenters_fit`` queues every pass.  ``cluster_centers_`` holds the chosen frames' ORIGINAL coordinates
+        on the host; ``inertia_`` is the library's ordered sum of ``distances_``."""
+        from .. import parallel
+        if parallel.active() or self._force_sharded:
+            raise NotImplementedError("the row-sharded k-centers fit does not take the rmsd metric")
+        frames = X if isinstance(X, libdistance.RmsdFrames) else libdistance.RmsdFrames(X)
+        n_samples = len(frames)
+        seed = check_random_state(self.random_state).randint(0, n_samples)
+        K = int(self.n_clusters)
+        ids = np.zeros(K, dtype=np.int64)
+        labels = empty_like_placement(frames._arr, (n_samples,), np.int64)
+        distances = empty_like_placement(frames._arr, (n_samples,), np.float64)
+        al, ad = Arr(labels, np.int64), Arr(distances, np.float64)
+        inertia = C.c_double(0.0)
+        check(_lib.lib().msm_rmsd_kcenters_fit(frames.handle, K, int(seed), ids.ctypes.data, al.vp, ad.vp, C.byref(inertia),
+                                               frames.on_device))
+        self.labels_ = labels
+        self.distances_ = distances
+        self.cluster_ids_ = ids.tolist()
+        self.cluster_centers_ = frames.frames(ids)
+        self.inertia_ = float(inertia.value)
         return self
 
     def _fit_sharded(self, X, metric):
@@ -148,6 +176,8 @@ class _KCenters(ClusterMixin, TransformerMixin):
     def predict(self, X):
         """Index of the closest cluster centre for each sample in X
         (kcenters.py:104-126 -> libdistance.assign_nearest)."""
+        if libdistance.is_rmsd(self.metric) and libdistance.conformations(X) is not None:
+            return libdistance.assign_nearest(X, self.cluster_centers_, metric="rmsd")[0]
         X = _as_float(X)
         centers = self.cluster_centers_
         if is_device_array(centers):
@@ -171,9 +201,11 @@ class KCenters(MultiSequenceClusterMixin, _KCenters, BaseEstimator):
     labels_ : list with one int array per input sequence (label of every frame)
     distances_ : list with one float64 array per input sequence (distance of every frame to its centre)
     '''
+    _takes_rmsd = True
 
     def fit(self, sequences, y=None):
-        """Fit the kcenters clustering on a list of [sequence_length, n_features] arrays."""
+        """Fit the kcenters clustering on a list of [sequence_length, n_features] arrays (with the rmsd metric:
+        [sequence_length, n_atoms, 3] conformations)."""
         MultiSequenceClusterMixin.fit(self, sequences)
         self.distances_ = self._split(self.distances_)
         return self

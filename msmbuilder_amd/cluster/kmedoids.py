@@ -100,9 +100,31 @@ def kmedoids_fit(ax, metric, n_clusters, n_pass, init, X_indices=None):
     return ids.astype(np.intp), error.value, int(ifound.value)
 
 
+def rmsd_input(est, X):
+    """Prepared frames when the estimator's metric is rmsd and X is a set of conformations, else None."""
+    if libdistance.is_rmsd(est.metric) and libdistance.conformations(X) is not None:
+        return X if isinstance(X, libdistance.RmsdFrames) else libdistance.RmsdFrames(X)
+    return None
+
+
+def kmedoids_fit_rmsd(frames, n_clusters, n_pass, init, X_indices=None):
+    """``kmedoids_fit`` for conformations: ``msm_rmsd_pdist`` of the (indexed) frames into device memory, then the
+    existing loop ``msm_kmedoids`` over that matrix where it lies."""
+    dmat = libdistance.rmsd_pdist(frames, X_indices, device=True)
+    n = len(frames) if X_indices is None else len(X_indices)
+    init = np.ascontiguousarray(init, dtype=np.int64).reshape(max(n_pass, 1), n)
+    ids = np.zeros(n, dtype=np.int64)
+    error, ifound = C.c_double(0.0), C.c_int64(0)
+    check(_lib.lib().msm_kmedoids(Arr(dmat, np.float64).vp, n, int(n_clusters), int(n_pass), init.ctypes.data, ids.ctypes.data,
+                                  C.byref(error), C.byref(ifound), 1))
+    return ids.astype(np.intp), error.value, int(ifound.value)
+
+
 def nearest_centre(est, X):
     """``predict`` of both k-medoids estimators: the exact ``assign_nearest`` kernel against the fitted centres, on rows
     cast by the fit's dtype rule."""
+    if rmsd_input(est, X) is not None:
+        return libdistance.assign_nearest(X, est.cluster_centers_, metric="rmsd")[0]
     ax = working_array(X)
     return libdistance.assign_nearest(ax.keep, est.cluster_centers_, metric=vector_metric(est.metric))[0]
 
@@ -130,7 +152,8 @@ class _KMedoids(ClusterMixin, TransformerMixin):
         assignment; the pass with the lowest summed distance is kept.
     metric : str (default "euclidean")
         One of libdistance's vector metrics: euclidean, sqeuclidean, cityblock, chebyshev, canberra, braycurtis,
-        hamming, jaccard.  (The reference's "rmsd" needs mdtraj trajectories and is out of scope.)
+        hamming, jaccard -- or "rmsd" for conformations: float32 (n_frames, n_atoms, 3) arrays, torch CUDA tensors or
+        objects with such an ``.xyz``; ``cluster_centers_`` is then a host (n_clusters, n_atoms, 3) array.
     random_state : integer or numpy.RandomState, optional
         The generator of the initial assignments.  An integer fixes the seed; the default is numpy's global one.
 
@@ -163,13 +186,22 @@ class _KMedoids(ClusterMixin, TransformerMixin):
             raise ValueError('n_passes must be greater than 0. got %s' % self.n_passes)
         if self.n_clusters < 1:
             raise ValueError('n_passes must be greater than 0. got %s' % self.n_clusters)
-        metric = vector_metric(self.metric)
-        ax = working_array(X)
-        n = ax.shape[0]
+        frames = rmsd_input(self, X)
+        if frames is None:
+            metric = vector_metric(self.metric)
+            ax = working_array(X)
+        n = len(frames) if frames is not None else ax.shape[0]
         if self.n_clusters > n:
             raise ValueError('Number of clusters requested (%d) greater than number of elements (%d)'
                              % (self.n_clusters, n))
         init = random_assignments(check_random_state(self.random_state), n, self.n_clusters, self.n_passes)
+        if frames is not None:
+            # conformations: the condensed rmsd matrix on the device, then the same loop; the centres are the medoids'
+            # original coordinates, host (n_clusters, n_atoms, 3)
+            ids, self.inertia_, _ = kmedoids_fit_rmsd(frames, self.n_clusters, self.n_passes, init)
+            self.labels_, self.cluster_ids_ = contigify_ids(ids)
+            self.cluster_centers_ = frames.frames(self.cluster_ids_)
+            return self
         ids, self.inertia_, _ = kmedoids_fit(ax, metric, self.n_clusters, self.n_passes, init)
         self.labels_, self.cluster_ids_ = contigify_ids(ids)
         # cluster_centers_ (kmedoids.py:98: X[cluster_ids_]) is a HOST array like the other clusterers': predict needs it there
@@ -193,6 +225,7 @@ class KMedoids(MultiSequenceClusterMixin, _KMedoids, BaseEstimator):
     labels_ : list of arrays, one per sequence, each label in [0, n_clusters)
     inertia_ : float
     '''
+    _takes_rmsd = True
 
     def fit(self, sequences, y=None):
         """Fit the clustering on a list of [sequence_length, n_features] arrays."""

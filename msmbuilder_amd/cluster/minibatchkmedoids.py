@@ -15,11 +15,12 @@ import numpy as np
 from sklearn.base import ClusterMixin, TransformerMixin
 from sklearn.utils import check_random_state
 
-from .. import _lib
+from .. import _lib, libdistance
 from .._lib import Arr, check, empty_like_placement
 from ..base import BaseEstimator
 from .base import MultiSequenceClusterMixin
-from .kmedoids import contigify_ids, kmedoids_fit, nearest_centre, vector_metric, working_array
+from .kmedoids import (contigify_ids, kmedoids_fit, kmedoids_fit_rmsd, nearest_centre, rmsd_input, vector_metric,
+                       working_array)
 from .minibatchkmeans import _rows_to_host
 
 __all__ = ['MiniBatchKMedoids']
@@ -61,7 +62,8 @@ class _MiniBatchKMedoids(ClusterMixin, TransformerMixin):
         Size of the mini batches.
     metric : str (default "euclidean")
         One of libdistance's vector metrics: euclidean, sqeuclidean, cityblock, chebyshev, canberra, braycurtis,
-        hamming, jaccard.  (The reference's "rmsd" needs mdtraj trajectories and is out of scope.)
+        hamming, jaccard -- or "rmsd" for conformations: float32 (n_frames, n_atoms, 3) arrays, torch CUDA tensors or
+        objects with such an ``.xyz``; ``cluster_centers_`` is then a host (n_clusters, n_atoms, 3) array.
     max_no_improvement : int, default: 10
         Stop after this many consecutive mini batches that change no assignment.
     random_state : integer or numpy.RandomState, optional
@@ -94,9 +96,11 @@ class _MiniBatchKMedoids(ClusterMixin, TransformerMixin):
         self.random_state = random_state
 
     def fit(self, X, y=None):
-        metric = vector_metric(self.metric)
-        ax = working_array(X)
-        n, K, B = ax.shape[0], self.n_clusters, self.batch_size
+        frames = rmsd_input(self, X)   # conformations: prepared once, every batch gathers from the same image
+        if frames is None:
+            metric = vector_metric(self.metric)
+            ax = working_array(X)
+        n, K, B = len(frames) if frames is not None else ax.shape[0], self.n_clusters, self.batch_size
         rs = check_random_state(self.random_state)
         # the generator is used exactly as the reference uses it (minibatchkmedoids.py:89-98): K centre rows, one label
         # per row, then B row indices per step
@@ -109,7 +113,10 @@ class _MiniBatchKMedoids(ClusterMixin, TransformerMixin):
             rows = np.concatenate([centres, rs.randint(0, n, B)]).astype(np.intp)
             # positions 0 .. K-1 are the centres, each starting in its own cluster; a batch row starts where it is now
             start = np.concatenate([own, labels[rows[K:]]])
-            medoids, _, _ = kmedoids_fit(ax, metric, K, 0, start, X_indices=rows)
+            if frames is not None:
+                medoids, _, _ = kmedoids_fit_rmsd(frames, K, 0, start, X_indices=rows)
+            else:
+                medoids, _, _ = kmedoids_fit(ax, metric, K, 0, start, X_indices=rows)
             self.n_steps_ += 1
             new_labels, positions = contigify_ids(medoids)   # clusters renumbered by first appearance over the positions
             centres = rows[positions]
@@ -122,6 +129,12 @@ class _MiniBatchKMedoids(ClusterMixin, TransformerMixin):
                 break
 
         self.cluster_ids_ = centres
+        if frames is not None:
+            self.cluster_centers_ = frames.frames(centres)
+            self.labels_, dist, _ = libdistance.rmsd_assign(frames, libdistance.RmsdFrames(self.cluster_centers_))
+            dist = dist.cpu().numpy() if frames.on_device else dist
+            self.inertia_ = float(np.add.accumulate(dist)[-1]) if n else 0.0   # in row order, as below
+            return self
         self.cluster_centers_ = _rows_to_host(ax, centres)
         self.labels_, self.inertia_ = assign_ordered(ax, self.cluster_centers_, metric)
         return self
@@ -144,6 +157,7 @@ class MiniBatchKMedoids(MultiSequenceClusterMixin, _MiniBatchKMedoids, BaseEstim
     labels_ : list of arrays, one per sequence, each label in [0, n_clusters)
     inertia_ : float
     '''
+    _takes_rmsd = True
 
     def fit(self, sequences, y=None):
         """Fit the clustering on a list of [sequence_length, n_features] arrays."""
