@@ -31,6 +31,8 @@
  *                     (cluster/kmedoids.py:91, cluster/minibatchkmedoids.py:83)
  *   msm_linkage* / msm_landmark_*  cluster/agglomerative.py:183-221 (pdist, the fastcluster linkage call, the loop over
  *                     all pairs) and :248-273 (predict: cdist + pooling per cluster)
+ *   msm_divergence_*  utils/divergence.py:14-72 (the nested loops over rows and columns), as MVCA (lumping/mvca.py) runs them
+ *                     through cluster/agglomerative.py:50-69
  *   msm_kmeans_* / msm_mbk_*  sklearn MiniBatchKMeans arithmetic behind
  *                     cluster/__init__.py:67-69 (third-party)
  * The exact reference signatures of libdistance are additionally exported,
@@ -568,6 +570,58 @@ int msm_landmark_predict_f64(const double* X, msm_idx_t n, msm_idx_t m, const do
                              const msm_idx_t* offsets, msm_idx_t K, const double* intra, const char* metric,
                              const char* pooling, msm_idx_t* labels, double* pooled, int* negative, int on_device);
 int msm_landmark_predict_plan(msm_idx_t m, int elem_size, msm_idx_t* out4);
+/* The same pooling over a distance matrix: D is n x L float64 at row stride ld >= L elements (follows on_device, like
+ * labels and pooled), its columns the landmarks permuted by cluster as above; offsets and intra are host arrays.  The
+ * pooling code is the one msm_landmark_predict_* runs: fed that metric's float64 cdist it returns the same labels and
+ * pooled values.  A host matrix travels in blocks of rows through the scratch described below.
+ *
+ * The three symmetric divergences ("js_metric", "js_divergence", "sym_kl_divergence", see msm_divergence_*) are accepted
+ * as `metric` by msm_linkage_fit_* (their condensed pdist takes the vector metric's place) and by
+ * msm_landmark_predict_* (the divergence cdist of a block of rows against the landmarks is written to a scratch buffer
+ * of the library and pooled by the matrix kernel, block after block).  The scratch holds at most 64 MiB, or 256 rows x L
+ * doubles where that is larger.  "kl_divergence" is refused with MSM_ERR_METRIC: it is not symmetric. */
+int msm_landmark_predict_dmat(const double* D, msm_idx_t n, msm_idx_t L, msm_idx_t ld, const msm_idx_t* offsets, msm_idx_t K,
+                              const double* intra, const char* pooling, msm_idx_t* labels, double* pooled, int* negative,
+                              int on_device);
+/* Every row against every row, from the condensed matrix of the n rows themselves (n >= 2; follows on_device, like labels
+ * and pooled): blocks of rows of its square form -- the columns in the order perm (host, n entries in [0, n): the rows
+ * permuted by cluster), the diagonal exactly 0 -- are expanded into the same scratch and pooled.  For a symmetric distance
+ * with d(i, i) = 0 this is msm_landmark_predict_* of the rows against themselves, bit for bit, without computing a
+ * distance twice. */
+int msm_landmark_predict_condensed(const double* dmat, msm_idx_t n, const msm_idx_t* perm, const msm_idx_t* offsets, msm_idx_t K,
+                                   const double* intra, const char* pooling, msm_idx_t* labels, double* pooled, int* negative,
+                                   int on_device);
+
+/* ---- KL-family divergences between non-negative rows (utils/divergence.py) ----------------------------------------------
+ * kind: "kl_divergence" | "sym_kl_divergence" | "js_divergence" | "js_metric".  In float64 (float32 rows are widened
+ * exactly; the output is always float64), the reference's manual loop:
+ *     kl(P, Q)  = max(sum_k [P_k * Q_k != 0] P_k * log(P_k / Q_k), 0)     ascending k; a NaN sum stays NaN
+ *     sym_kl    = kl(P, Q) + kl(Q, P)
+ *     js        = 0.5 * kl(P, M) + 0.5 * kl(Q, M),  M_k = (P_k + Q_k) / 2
+ *     js_metric = sqrt(js)
+ * A term is skipped where the float64 product is zero (an underflowing product included): q = 0 under p > 0 adds nothing.
+ * Each pair's sum is built by one thread in ascending k; no atomics.  cdist, pdist and rows give the same bits for the
+ * same pair of rows, d(i, j) == d(j, i) bit for bit for the three symmetric kinds, and d(i, i) == 0.
+ *   msm_divergence_cdist_*: out[i * nB + j] = div(XA[i], XB[j]); XA, XB and out follow on_device.
+ *   msm_divergence_pdist_*: condensed (i < j, scipy's order) over the rows of X or the rows X_indices names (may repeat a
+ *     row; host indices are range-checked); X, X_indices and out follow on_device.
+ *   msm_divergence_rows_*: out[r] = div(P[r], Q[r]) for n pairs of HOST rows.
+ *   msm_divergence_plan: out4 = {tile rows, tile columns, columns per LDS chunk, threads per workgroup}.
+ *   msm_divergence_log_probe: out[i] = log(x[i]) on the device for reps == 1, a sum of reps logs of slowly growing
+ *     arguments otherwise (HOST arrays); *ms (nullable) = the kernel's time.  For the accuracy and throughput probe.
+ * MSM_ERR_METRIC: unknown or null kind; MSM_ERR_INVALID: null pointers, m < 1, negative sizes. */
+int msm_divergence_cdist_f32(const float* XA, msm_idx_t nA, const float* XB, msm_idx_t nB, msm_idx_t m, const char* kind,
+                             double* out, int on_device);
+int msm_divergence_cdist_f64(const double* XA, msm_idx_t nA, const double* XB, msm_idx_t nB, msm_idx_t m, const char* kind,
+                             double* out, int on_device);
+int msm_divergence_pdist_f32(const float* X, msm_idx_t n, msm_idx_t m, const msm_idx_t* X_indices, msm_idx_t n_idx,
+                             const char* kind, double* out, int on_device);
+int msm_divergence_pdist_f64(const double* X, msm_idx_t n, msm_idx_t m, const msm_idx_t* X_indices, msm_idx_t n_idx,
+                             const char* kind, double* out, int on_device);
+int msm_divergence_rows_f32(const float* P, const float* Q, msm_idx_t n, msm_idx_t m, const char* kind, double* out);
+int msm_divergence_rows_f64(const double* P, const double* Q, msm_idx_t n, msm_idx_t m, const char* kind, double* out);
+int msm_divergence_plan(msm_idx_t* out4);
+int msm_divergence_log_probe(const double* x, msm_idx_t n, int reps, double* out, float* ms);
 
 /* ---- Nystroem kernel feature map (decomposition/kernel_approximation.py, ktica.py) ------------------------------------
  * out[i, :] = k(rows[i], landmarks) . B - c     (rows: n x n_features at row stride ld elements; landmarks: L x

@@ -11,6 +11,12 @@ the (L-1) x 4 linkage matrix), ``msm_landmark_within`` adds the squared distance
 cluster and keeps the running minimum, so the N x L matrix is never formed.  Only ``fcluster`` on the small linkage
 matrix, ``bincount`` and the L x F means of ``cluster_centers_`` run on the host.
 
+Besides libdistance's vector metrics the three symmetric divergences of ``utils.divergence`` (``js_metric``,
+``js_divergence``, ``sym_kl_divergence``, by name or as their ``*_array`` functions) are metrics here: the fit queues the
+divergence tile kernel's condensed matrix in the vector pdist's place, and predict computes the divergences of blocks of
+rows to the landmarks into a bounded scratch buffer and pools each block with the same pooling code
+(``msm_landmark_predict_dmat``'s kernel).  That is what ``lumping.MVCA`` is assembled from.
+
 Ties: the pair of lowest distance is merged; among equal distances the lowest row slot, then the lowest column slot,
 where a merged cluster lives on in the higher of its two slots.  ``average`` and ``ward`` pooled values are sums of one
 term per landmark in ascending landmark order within the cluster (numpy's ``mean`` / ``sum`` add pairwise): they agree
@@ -27,6 +33,7 @@ from sklearn.utils import check_random_state
 from .. import _lib, libdistance
 from .._lib import Arr, check
 from ..base import BaseEstimator
+from ..utils import divergence
 from .base import MultiSequenceClusterMixin
 from .kmedoids import working_array
 from .minibatchkmeans import _rows_to_host
@@ -37,15 +44,25 @@ LINKAGES = ('single', 'complete', 'average', 'ward')
 
 
 def landmark_metric(metric):
-    """One of libdistance's vector metrics; a callable or 'rmsd' (the reference's mdtraj paths) raises ValueError."""
+    """One of libdistance's vector metrics, or one of the three symmetric divergences of ``utils.divergence`` by name or
+    as its ``*_array`` function (recognised by identity); any other callable, ``kl_divergence`` (not symmetric) and
+    'rmsd' (the reference's mdtraj path) raise ValueError."""
     metric = metric.decode() if isinstance(metric, bytes) else metric
+    names = ', '.join("'%s'" % s for s in libdistance.VECTOR_METRICS[:8] + tuple(divergence.SYMMETRIC_KINDS))
     if callable(metric):
-        raise ValueError('a callable metric is not supported: metric must be one of %s'
-                         % ', '.join("'%s'" % s for s in libdistance.VECTOR_METRICS[:8]))
+        kind = divergence.ARRAY_FUNCTION_KINDS.get(metric)
+        if kind is None:
+            raise ValueError('a callable metric is not supported, except the sym_kl_divergence_array, js_divergence_array '
+                             'and js_metric_array of msmbuilder_amd.utils.divergence: metric must be one of %s' % names)
+        metric = kind
+    if metric == 'kl_divergence':
+        raise ValueError("metric 'kl_divergence' is not symmetric: use sym_kl_divergence, js_divergence or js_metric")
+    if metric in divergence.SYMMETRIC_KINDS:
+        return metric
     if metric == 'rmsd':
         raise ValueError("metric 'rmsd' needs mdtraj trajectories and is not supported")
     if metric not in libdistance.VECTOR_METRICS:
-        raise ValueError('metric must be one of %s' % ', '.join("'%s'" % s for s in libdistance.VECTOR_METRICS[:8]))
+        raise ValueError('metric must be one of %s' % names)
     return metric
 
 
@@ -125,6 +142,70 @@ def within_cluster(dmat, n, labels, n_clusters):
     return out
 
 
+def pooled_predict_dmat(D, offsets, intra, pooling, want_pooled=False):
+    """``msm_landmark_predict_dmat``: (labels, winning pooled values or None, negative flag) from an n x L float64 distance
+    matrix whose columns are the landmarks permuted by cluster.  ``D`` is a numpy array or a torch CUDA tensor; rows may
+    be strided (a view of a wider matrix), anything else is copied."""
+    if len(D.shape) != 2:
+        raise ValueError('D must be 2-dimensional')
+    on_device = int(_lib.is_device_array(D))
+    if on_device:
+        import torch
+        D = D.to(torch.float64)
+        if D.stride(1) != 1 or D.stride(0) < D.shape[1]:
+            D = D.contiguous()
+        ld, ptr = D.stride(0), D.data_ptr()
+        ref = Arr(D.new_empty(1))   # (selects the device and the stream)
+    else:
+        D = np.asarray(D, dtype=np.float64)
+        if D.strides[1] != 8 or D.strides[0] % 8 or D.strides[0] < 8 * D.shape[1]:
+            D = np.ascontiguousarray(D)
+        ld, ptr = D.strides[0] // 8, D.ctypes.data
+        ref = Arr(np.empty(1))
+    n, L = D.shape
+    ld = max(int(ld), L)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    K = len(offsets) - 1
+    intra = None if intra is None else np.ascontiguousarray(intra, dtype=np.float64)
+    if intra is not None and len(intra) != K:
+        raise ValueError('intra must have one entry per cluster')
+    labels = _lib.empty_like_placement(ref, (n,), np.int64)
+    pooled = _lib.empty_like_placement(ref, (n,), np.float64) if want_pooled else None
+    neg = C.c_int(0)
+    al = Arr(labels, np.int64) if n else None
+    ap = Arr(pooled, np.float64) if (want_pooled and n) else None
+    check(_lib.lib().msm_landmark_predict_dmat(
+        C.c_void_p(ptr) if n else None, n, L, ld, offsets.ctypes.data, K, intra.ctypes.data if intra is not None else None,
+        pooling.encode(), al.vp if al is not None else None, ap.vp if ap is not None else None, C.byref(neg), on_device))
+    return labels, pooled, bool(neg.value)
+
+
+def pooled_predict_condensed(dmat, n, perm, offsets, intra, pooling, want_pooled=False):
+    """``msm_landmark_predict_condensed``: every one of the n rows pooled against all of them from their own condensed
+    float64 matrix (numpy, or a torch CUDA tensor as :func:`msmbuilder_amd.utils.divergence.divergence_pdist` leaves it);
+    ``perm`` lists the rows by cluster.  (labels, winning pooled values or None, negative flag), placed like ``dmat``."""
+    ad = Arr(dmat, np.float64)
+    if ad.shape != (n * (n - 1) // 2,):
+        raise ValueError('dmat must be the condensed matrix of %d rows' % n)
+    perm = np.ascontiguousarray(perm, dtype=np.int64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    K = len(offsets) - 1
+    if perm.shape != (n,):
+        raise ValueError('perm must have one entry per row')
+    intra = None if intra is None else np.ascontiguousarray(intra, dtype=np.float64)
+    if intra is not None and len(intra) != K:
+        raise ValueError('intra must have one entry per cluster')
+    labels = _lib.empty_like_placement(ad, (n,), np.int64)
+    pooled = _lib.empty_like_placement(ad, (n,), np.float64) if want_pooled else None
+    neg = C.c_int(0)
+    al = Arr(labels, np.int64)
+    ap = Arr(pooled, np.float64) if want_pooled else None
+    check(_lib.lib().msm_landmark_predict_condensed(
+        ad.vp, n, perm.ctypes.data, offsets.ctypes.data, K, intra.ctypes.data if intra is not None else None, pooling.encode(),
+        al.vp, ap.vp if ap is not None else None, C.byref(neg), ad.on_device))
+    return labels, pooled, bool(neg.value)
+
+
 def pooled_predict(X, landmarks, offsets, intra, metric, pooling, want_pooled=False):
     """``msm_landmark_predict_*``: (labels, winning pooled values or None, negative flag).  ``landmarks`` are already
     permuted by cluster; labels and values live where X lives."""
@@ -172,8 +253,10 @@ class _LandmarkAgglomerative(ClusterMixin, TransformerMixin):
         cluster's landmarks with the same rule (``ward_predictor`` after a ward fit) and picks the lowest.
     metric : str, default="euclidean"
         One of libdistance's vector metrics: euclidean, sqeuclidean, cityblock, chebyshev, canberra, braycurtis,
-        hamming, jaccard.  (The reference's callable metrics and "rmsd" need mdtraj trajectories and are out of scope:
-        ``ValueError``.)
+        hamming, jaccard; or one of the symmetric divergences between non-negative rows, 'js_metric', 'js_divergence',
+        'sym_kl_divergence', by name or as the ``js_metric_array``, ``js_divergence_array``, ``sym_kl_divergence_array``
+        function of ``msmbuilder_amd.utils.divergence``.  (Any other callable, ``kl_divergence`` and "rmsd" are out of
+        scope: ``ValueError``.)
     landmark_strategy : {'stride', 'random'}, default='stride'
         "stride" takes every (n // n_landmarks)-th row, "random" draws rows uniformly with replacement.
     random_state : integer or numpy.RandomState, optional

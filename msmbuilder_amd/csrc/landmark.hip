@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "divergence_dev.h"
 #include "landmark_dev.h"
 
 namespace msm {
@@ -34,6 +35,17 @@ static int linkage_method(const char* name)
     for (int k = 0; k < LK_COUNT; ++k)
         if (!strcmp(name, names[k])) return k;
     return -1;
+}
+
+// A metric name of msm_linkage_fit_* / msm_landmark_predict_*: one of libdistance's vector metrics (*mid >= 0) or one of
+// the three symmetric divergences (*kind >= 0).  kl_divergence is refused: it is not symmetric.
+static int lm_metric(const char* metric, int* mid, int* kind)
+{
+    *kind = divergence_kind(metric);
+    *mid = *kind >= 0 ? -1 : metric_id(metric);
+    if (*kind == DV_KL) return fail(MSM_ERR_METRIC, "metric 'kl_divergence' is not symmetric: use sym_kl_divergence, js_divergence or js_metric");
+    if (*kind < 0 && *mid < 0) return fail(MSM_ERR_METRIC, "unknown metric '%s'", metric ? metric : "(null)");
+    return MSM_OK;
 }
 
 static int lk_validate(msm_idx_t n, const char* method, const double* Z)
@@ -95,18 +107,21 @@ template <typename T>
 static int linkage_fit_impl(const T* X, msm_idx_t n, msm_idx_t m, const char* metric, const msm_idx_t* X_indices,
                             msm_idx_t n_idx, const char* method, double* Z, int on_device)
 {
-    const int mid = metric_id(metric);
-    if (mid < 0) return fail(MSM_ERR_METRIC, "unknown metric '%s'", metric ? metric : "(null)");
+    int mid, kind, rc;
+    if ((rc = lm_metric(metric, &mid, &kind))) return rc;
     if (!X) return fail(MSM_ERR_INVALID, "linkage_fit: null pointer");
     if (n < 0 || m < 1 || (X_indices && n_idx < 0)) return fail(MSM_ERR_INVALID, "linkage_fit: bad shape");
     const msm_idx_t nn = X_indices ? n_idx : n;
-    int rc;
     if ((rc = lk_validate(nn, method, Z))) return rc;
     if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
     g_fit_n = 0;
     DevBuf& dOut = fit_buf();
     if ((rc = dOut.reserve((size_t)nn * (size_t)(nn - 1) / 2 * sizeof(double)))) return rc;
-    if ((rc = pdist_queue<T>(X, mid, n, m, X_indices, nn, on_device, dOut.as<double>()))) return rc;
+    if (kind >= 0)
+        rc = divergence_pdist_queue<T>(X, kind, n, m, X_indices, nn, on_device, dOut.as<double>());
+    else
+        rc = pdist_queue<T>(X, mid, n, m, X_indices, nn, on_device, dOut.as<double>());
+    if (rc) return rc;
     if ((rc = lk_run(dOut.as<double>(), nn, linkage_method(method), Z))) return rc;
     g_fit_n = nn;
     return MSM_OK;
@@ -155,13 +170,114 @@ static int pooling_id(const char* name)
     return linkage_method(name);   // the same four names, in LpPool's order
 }
 
+// The checks on the permuted landmarks' offsets that both predict forms share.
+static int lp_validate_offsets(const msm_idx_t* offsets, msm_idx_t K, msm_idx_t L)
+{
+    if (offsets[0] != 0 || offsets[K] != L) return fail(MSM_ERR_INVALID, "landmark_predict: offsets must run from 0 to the number of landmarks");
+    for (msm_idx_t c = 0; c < K; ++c)
+        if (offsets[c + 1] < offsets[c]) return fail(MSM_ERR_INVALID, "landmark_predict: offsets must not decrease");
+    return MSM_OK;
+}
+
+// Rows of an n x L float64 block whose pooled labels one launch takes: the library's scratch for the divergence predict
+// holds at most LD_SCRATCH_BYTES, or LP_T rows where one block of LP_T rows is larger than that.
+constexpr size_t LD_SCRATCH_BYTES = (size_t)64 << 20;
+static long long ld_block_rows(long long n, long long L)
+{
+    const long long fit = (long long)(LD_SCRATCH_BYTES / ((size_t)L * sizeof(double)));
+    return std::min<long long>(n, std::max<long long>(fit / LP_T * LP_T, LP_T));
+}
+
+static void launch_ld(const double* dD, long long n, long long L, long long ld, const long long* dOff, const double* dIntra, int pool_id,
+                      msm_idx_t* dLabels, double* dPooled, int* dNeg)
+{
+    LdArgs A;
+    memset(&A, 0, sizeof(A));
+    A.D = dD;
+    A.n = n;
+    A.L = L;
+    A.ld = ld;
+    A.off = dOff;
+    A.intra = dIntra;
+    A.labels = dLabels;
+    A.pooled = dPooled;
+    A.neg = dNeg;
+    A.pool = pool_id;
+    hipLaunchKernelGGL(lp_predict_dmat_kernel, dim3((int)ceil_div(n, LP_T)), dim3(LP_T), 0, stream(), A);
+}
+
+// The pooled labels of n rows from a distance matrix, queued; *dNeg is the device flag for ld_finish.  The matrix is one of
+//   D  (n x L at row stride ld): a device matrix is pooled in place, a host one travels in blocks of rows through the scratch;
+//   dC (DEVICE condensed matrix of n = L elements) with perm (host): blocks of rows of its square form, columns in perm's
+//      order and a zero diagonal, are expanded into the scratch.
+// labels and pooled follow on_device.
+static int ld_run(const double* D, const double* dC, const msm_idx_t* perm, long long n, long long L, long long ld,
+                  const msm_idx_t* offsets, msm_idx_t K, const double* intra, int pool_id, msm_idx_t* labels, double* pooled,
+                  int on_device, int** dNeg)
+{
+    int rc;
+    DevBuf &dOff = pool(PS_IDX), &dPar = pool(PS_PAR), &dLab = pool(PS_LAB), &dMin = pool(PS_MIN), &dD = pool(PS_OUT), &dPerm = pool(PS_IDS);
+    if ((rc = dOff.reserve((size_t)(K + 1) * sizeof(msm_idx_t)))) return rc;
+    if ((rc = dPar.reserve(16 + (size_t)K * sizeof(double)))) return rc;
+    MSM_HIP_CHECK(hipMemcpyAsync(dOff.p, offsets, (size_t)(K + 1) * sizeof(msm_idx_t), hipMemcpyHostToDevice, stream()));
+    MSM_HIP_CHECK(hipMemsetAsync(dPar.p, 0, 16, stream()));
+    if (intra)
+        MSM_HIP_CHECK(hipMemcpyAsync(dPar.as<char>() + 16, intra, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream()));
+    const long long* off = dOff.as<long long>();
+    const double* dIntra = reinterpret_cast<const double*>(dPar.as<char>() + 16);
+    *dNeg = dPar.as<int>();
+    msm_idx_t* dLabels = labels;
+    double* dPooled = pooled;
+    if (!on_device) {
+        if ((rc = dLab.reserve((size_t)n * sizeof(msm_idx_t)))) return rc;
+        if (pooled && (rc = dMin.reserve((size_t)n * sizeof(double)))) return rc;
+        dLabels = dLab.as<msm_idx_t>();
+        dPooled = pooled ? dMin.as<double>() : nullptr;
+    }
+    if (D && on_device) {
+        launch_ld(D, n, L, ld, off, dIntra, pool_id, dLabels, dPooled, *dNeg);
+    } else {
+        const long long RB = ld_block_rows(n, L);
+        if ((rc = dD.reserve((size_t)RB * (size_t)L * sizeof(double)))) return rc;
+        if (dC) {
+            if ((rc = dPerm.reserve((size_t)L * sizeof(msm_idx_t)))) return rc;
+            MSM_HIP_CHECK(hipMemcpyAsync(dPerm.p, perm, (size_t)L * sizeof(msm_idx_t), hipMemcpyHostToDevice, stream()));
+        }
+        for (long long r0 = 0; r0 < n; r0 += RB) {
+            const long long rb = std::min<long long>(RB, n - r0);
+            if (dC)
+                hipLaunchKernelGGL(lp_expand_rows_kernel, dim3((int)std::min<long long>(ceil_div(rb * L, LP_T), 65536)), dim3(LP_T), 0, stream(),
+                                   dC, n, dPerm.as<long long>(), r0, rb, dD.as<double>());
+            else
+                MSM_HIP_CHECK(hipMemcpy2DAsync(dD.p, (size_t)L * sizeof(double), D + r0 * ld, (size_t)ld * sizeof(double),
+                                               (size_t)L * sizeof(double), (size_t)rb, hipMemcpyHostToDevice, stream()));
+            launch_ld(dD.as<double>(), rb, L, L, off, dIntra, pool_id, dLabels + r0, dPooled ? dPooled + r0 : nullptr, *dNeg);
+        }
+    }
+    MSM_HIP_CHECK(hipGetLastError());
+    if (!on_device) {
+        MSM_HIP_CHECK(hipMemcpyAsync(labels, dLabels, (size_t)n * sizeof(msm_idx_t), hipMemcpyDeviceToHost, stream()));
+        if (pooled) MSM_HIP_CHECK(hipMemcpyAsync(pooled, dPooled, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    }
+    return MSM_OK;
+}
+
+static int ld_finish(const int* dNeg, int* negative)
+{
+    int neg = 0;
+    MSM_HIP_CHECK(hipMemcpyAsync(&neg, dNeg, sizeof(int), hipMemcpyDeviceToHost, stream()));
+    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
+    *negative = neg;
+    return MSM_OK;
+}
+
 template <typename T>
 static int predict_impl(const T* X, msm_idx_t n, msm_idx_t m, const T* landmarks, msm_idx_t L, const msm_idx_t* offsets,
                         msm_idx_t K, const double* intra, const char* metric, const char* pooling, msm_idx_t* labels,
                         double* pooled, int* negative, int on_device)
 {
-    const int mid = metric_id(metric);
-    if (mid < 0) return fail(MSM_ERR_METRIC, "unknown metric '%s'", metric ? metric : "(null)");
+    int mid, kind, rc;
+    if ((rc = lm_metric(metric, &mid, &kind))) return rc;
     const int pool_id = pooling_id(pooling);
     if (pool_id < 0) return fail(MSM_ERR_INVALID, "linkage %s is not supported", pooling ? pooling : "(null)");
     if (!landmarks || !offsets || !negative || (n > 0 && (!X || !labels)))
@@ -169,13 +285,10 @@ static int predict_impl(const T* X, msm_idx_t n, msm_idx_t m, const T* landmarks
     if (pool_id == LP_WARD && !intra) return fail(MSM_ERR_INVALID, "landmark_predict: ward pooling needs the within-cluster sums");
     if (n < 0 || m < 1 || L < 1 || K < 1 || m > INT32_MAX / 2 || L > INT32_MAX / 2)
         return fail(MSM_ERR_INVALID, "landmark_predict: bad shape");
-    if (offsets[0] != 0 || offsets[K] != L) return fail(MSM_ERR_INVALID, "landmark_predict: offsets must run from 0 to the number of landmarks");
-    for (msm_idx_t c = 0; c < K; ++c)
-        if (offsets[c + 1] < offsets[c]) return fail(MSM_ERR_INVALID, "landmark_predict: offsets must not decrease");
+    if ((rc = lp_validate_offsets(offsets, K, L))) return rc;
     *negative = 0;
     if (n == 0) return MSM_OK;
     if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
-    int rc;
     DevBuf &dX = pool(PS_X), &dY = pool(PS_Y), &dOff = pool(PS_IDX), &dPar = pool(PS_PAR), &dLab = pool(PS_LAB), &dMin = pool(PS_MIN);
     if ((rc = dY.reserve((size_t)L * m * sizeof(T)))) return rc;
     if ((rc = dOff.reserve((size_t)(K + 1) * sizeof(msm_idx_t)))) return rc;
@@ -212,7 +325,21 @@ static int predict_impl(const T* X, msm_idx_t n, msm_idx_t m, const T* landmarks
             P.pooled = dMin.as<double>();
         }
     }
-    launch_lp<T>(mid, (int)ceil_div(n, LP_T), P);
+    if (kind >= 0) {
+        // a divergence: its cdist in blocks of rows into the library's scratch, each block pooled by the matrix kernel
+        const long long RB = ld_block_rows(n, L);
+        DevBuf& dD = pool(PS_OUT);
+        if ((rc = dD.reserve((size_t)RB * (size_t)L * sizeof(double)))) return rc;
+        for (long long r0 = 0; r0 < n; r0 += RB) {
+            const long long rb = std::min<long long>(RB, n - r0);
+            if ((rc = divergence_tile_queue<T>(kind, static_cast<const T*>(P.X) + r0 * m, nullptr, rb, static_cast<const T*>(P.Lm), nullptr,
+                                               L, m, dD.as<double>(), 0)))
+                return rc;
+            launch_ld(dD.as<double>(), rb, L, L, P.off, P.intra, pool_id, P.labels + r0, P.pooled ? P.pooled + r0 : nullptr, P.neg);
+        }
+    } else {
+        launch_lp<T>(mid, (int)ceil_div(n, LP_T), P);
+    }
     MSM_HIP_CHECK(hipGetLastError());
     if (!on_device) {
         MSM_HIP_CHECK(hipMemcpyAsync(labels, P.labels, (size_t)n * sizeof(msm_idx_t), hipMemcpyDeviceToHost, stream()));
@@ -327,6 +454,52 @@ int msm_landmark_predict_f64(const double* X, msm_idx_t n, msm_idx_t m, const do
                              msm_idx_t* labels, double* pooled, int* negative, int on_device)
 {
     return predict_impl<double>(X, n, m, landmarks, L, offsets, K, intra, metric, pooling, labels, pooled, negative, on_device);
+}
+
+int msm_landmark_predict_dmat(const double* D, msm_idx_t n, msm_idx_t L, msm_idx_t ld, const msm_idx_t* offsets, msm_idx_t K,
+                              const double* intra, const char* pooling, msm_idx_t* labels, double* pooled, int* negative, int on_device)
+{
+    const int pool_id = pooling_id(pooling);
+    if (pool_id < 0) return fail(MSM_ERR_INVALID, "linkage %s is not supported", pooling ? pooling : "(null)");
+    if (!offsets || !negative || (n > 0 && (!D || !labels))) return fail(MSM_ERR_INVALID, "landmark_predict_dmat: null pointer");
+    if (pool_id == LP_WARD && !intra) return fail(MSM_ERR_INVALID, "landmark_predict_dmat: ward pooling needs the within-cluster sums");
+    if (n < 0 || L < 1 || K < 1 || ld < L || L > INT32_MAX / 2) return fail(MSM_ERR_INVALID, "landmark_predict_dmat: bad shape");
+    int rc;
+    if ((rc = lp_validate_offsets(offsets, K, L))) return rc;
+    *negative = 0;
+    if (n == 0) return MSM_OK;
+    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
+    int* dNeg = nullptr;
+    if ((rc = ld_run(D, nullptr, nullptr, n, L, ld, offsets, K, intra, pool_id, labels, pooled, on_device, &dNeg))) return rc;
+    return ld_finish(dNeg, negative);
+}
+
+int msm_landmark_predict_condensed(const double* dmat, msm_idx_t n, const msm_idx_t* perm, const msm_idx_t* offsets, msm_idx_t K,
+                                   const double* intra, const char* pooling, msm_idx_t* labels, double* pooled, int* negative,
+                                   int on_device)
+{
+    const int pool_id = pooling_id(pooling);
+    if (pool_id < 0) return fail(MSM_ERR_INVALID, "linkage %s is not supported", pooling ? pooling : "(null)");
+    if (!dmat || !perm || !offsets || !negative || !labels) return fail(MSM_ERR_INVALID, "landmark_predict_condensed: null pointer");
+    if (pool_id == LP_WARD && !intra) return fail(MSM_ERR_INVALID, "landmark_predict_condensed: ward pooling needs the within-cluster sums");
+    if (n < 2 || K < 1 || n > INT32_MAX / 2) return fail(MSM_ERR_INVALID, "landmark_predict_condensed: bad shape");
+    for (msm_idx_t i = 0; i < n; ++i)
+        if (perm[i] < 0 || perm[i] >= n) return fail(MSM_ERR_INVALID, "landmark_predict_condensed: perm[%lld] is outside [0, %lld)", (long long)i, (long long)n);
+    int rc;
+    if ((rc = lp_validate_offsets(offsets, K, n))) return rc;
+    *negative = 0;
+    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
+    const double* dC = dmat;
+    if (!on_device) {
+        DevBuf& bC = pool(PS_X);
+        const size_t bytes = (size_t)n * (size_t)(n - 1) / 2 * sizeof(double);
+        if ((rc = bC.reserve(bytes))) return rc;
+        if ((rc = h2d_bulk(bC.p, dmat, bytes))) return rc;
+        dC = bC.as<double>();
+    }
+    int* dNeg = nullptr;
+    if ((rc = ld_run(nullptr, dC, perm, n, n, n, offsets, K, intra, pool_id, labels, pooled, on_device, &dNeg))) return rc;
+    return ld_finish(dNeg, negative);
 }
 
 int msm_landmark_predict_plan(msm_idx_t m, int elem_size, msm_idx_t* out4)

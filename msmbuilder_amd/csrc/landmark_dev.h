@@ -295,37 +295,25 @@ struct LpArgs {
     int TL, FCH;
 };
 
-template <typename T, int M, bool REG>
-__global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
-{
-    constexpr int E = LP_LDS / (int)sizeof(T);
-    constexpr int FC = FeatChunk<T>::FC;
-    __shared__ T Ls[E];
-    const T* __restrict__ X = static_cast<const T*>(P.X);
-    const T* __restrict__ Lm = static_cast<const T*>(P.Lm);
-    const int tid = threadIdx.x;
-    const long long row = (long long)blockIdx.x * LP_T + tid, m = P.m, L = P.L;
-    const bool valid = row < P.n;
-    const T* xr = X + (valid ? row : 0) * m;
-    const int pool = P.pool;
-
-    T x[REG ? FC : 1];   // narrow rows stay in registers
-    if constexpr (REG) {
-#pragma unroll
-        for (int f = 0; f < FC; ++f) x[f] = (valid && f < m) ? xr[f] : (T)0;
-    }
-
+// The pooling state of one row: the landmark l's distance d joins its cluster, and the cluster is closed at its last
+// landmark.  Shared by the fused kernel below and the distance-matrix form (lp_predict_dmat_kernel).
+struct LpPooler {
+    const long long* off;
+    const double* intra;
+    int pool;
     double best = INFINITY, acc = 0.0;
     long long label = 0, c = -1, cstart = 0, cend = 0;
     bool negative = false;
 
-    // the landmark l's distance d joins its cluster; the cluster is closed at its last landmark
-    auto step = [&](long long l, double d) {
+    __device__ __forceinline__ LpPooler(const long long* off_, const double* intra_, int pool_) : off(off_), intra(intra_), pool(pool_) {}
+
+    __device__ __forceinline__ void step(long long l, double d)
+    {
         if (l >= cend) {
             do {   // the next cluster with a landmark (l < L = off[K]: there is one)
                 ++c;
                 cstart = cend;
-                cend = P.off[c + 1];
+                cend = off[c + 1];
             } while (l >= cend);
             acc = pool == LP_SINGLE ? INFINITY : pool == LP_COMPLETE ? -INFINITY : 0.0;
         }
@@ -342,7 +330,7 @@ __global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
             double v = acc;
             if (pool == LP_AVERAGE) v = acc / cnt;
             if (pool == LP_WARD) {
-                v = (cnt * acc - P.intra[c]) / (cnt * (cnt + 1.0) / 2.0);
+                v = (cnt * acc - intra[c]) / (cnt * (cnt + 1.0) / 2.0);
                 negative |= v < 0.0;
             }
             if (v < best) {
@@ -350,7 +338,28 @@ __global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
                 label = c;
             }
         }
-    };
+    }
+};
+
+template <typename T, int M, bool REG>
+__global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
+{
+    constexpr int E = LP_LDS / (int)sizeof(T);
+    constexpr int FC = FeatChunk<T>::FC;
+    __shared__ T Ls[E];
+    const T* __restrict__ X = static_cast<const T*>(P.X);
+    const T* __restrict__ Lm = static_cast<const T*>(P.Lm);
+    const int tid = threadIdx.x;
+    const long long row = (long long)blockIdx.x * LP_T + tid, m = P.m, L = P.L;
+    const bool valid = row < P.n;
+    const T* xr = X + (valid ? row : 0) * m;
+    T x[REG ? FC : 1];   // narrow rows stay in registers
+    if constexpr (REG) {
+#pragma unroll
+        for (int f = 0; f < FC; ++f) x[f] = (valid && f < m) ? xr[f] : (T)0;
+    }
+
+    LpPooler pl(P.off, P.intra, P.pool);
 
     if (P.FCH == m) {
         for (long long l0 = 0; l0 < L; l0 += P.TL) {
@@ -370,7 +379,7 @@ __global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
                 } else {
                     for (int f = 0; f < (int)m; ++f) m_update<T, M>(a, b, xr[f], lv[f]);
                 }
-                step(l0 + t, m_final<M>(a, b, m));
+                pl.step(l0 + t, m_final<M>(a, b, m));
             }
         }
     } else {
@@ -384,13 +393,66 @@ __global__ __launch_bounds__(LP_T) void lp_predict_kernel(LpArgs P)
                 if (valid)
                     for (int f = 0; f < fw; ++f) m_update<T, M>(a, b, xr[f0 + f], Ls[f]);
             }
-            if (valid) step(l, m_final<M>(a, b, m));
+            if (valid) pl.step(l, m_final<M>(a, b, m));
         }
     }
     if (valid) {
-        P.labels[row] = label;
-        if (P.pooled) P.pooled[row] = best;
-        if (negative) *P.neg = 1;
+        P.labels[row] = pl.label;
+        if (P.pooled) P.pooled[row] = pl.best;
+        if (pl.negative) *P.neg = 1;
+    }
+}
+
+// The same pooling over a row-major n x L float64 distance matrix (row stride ld) whose columns are the landmarks permuted
+// by cluster: for metrics whose distances are computed by another kernel (the divergences).  One lane per row; the matrix
+// goes through LDS in tiles of LD_TC columns so that the loads run along the rows.
+constexpr int LD_TC = 16;
+
+struct LdArgs {
+    const double* D;
+    long long n, L, ld;
+    const long long* off;
+    const double* intra;
+    msm_idx_t* labels;
+    double* pooled;
+    int* neg;
+    int pool;
+};
+
+__global__ __launch_bounds__(LP_T) void lp_predict_dmat_kernel(LdArgs P)
+{
+    __shared__ double Ds[LP_T * (LD_TC + 1)];
+    const int tid = threadIdx.x;
+    const long long row0 = (long long)blockIdx.x * LP_T, row = row0 + tid;
+    const bool valid = row < P.n;
+    LpPooler pl(P.off, P.intra, P.pool);
+    for (long long l0 = 0; l0 < P.L; l0 += LD_TC) {
+        const int tc = (int)(P.L - l0 < LD_TC ? P.L - l0 : LD_TC);
+        __syncthreads();   // the previous tile has been read
+        for (int e = tid; e < LP_T * LD_TC; e += LP_T) {
+            const int r = e / LD_TC, c = e - r * LD_TC;
+            Ds[r * (LD_TC + 1) + c] = (row0 + r < P.n && c < tc) ? P.D[(row0 + r) * P.ld + l0 + c] : 0.0;
+        }
+        __syncthreads();
+        if (valid)
+            for (int t = 0; t < tc; ++t) pl.step(l0 + t, Ds[tid * (LD_TC + 1) + t]);
+    }
+    if (valid) {
+        P.labels[row] = pl.label;
+        if (P.pooled) P.pooled[row] = pl.best;
+        if (pl.negative) *P.neg = 1;
+    }
+}
+
+// Rows r0 .. r0 + rb - 1 of the square form of a condensed matrix of n elements, the columns taken in the order perm
+// (the landmarks permuted by cluster), the diagonal exactly zero: out is rb x n, row-major.
+__global__ __launch_bounds__(LP_T) void lp_expand_rows_kernel(const double* __restrict__ C, long long n, const long long* __restrict__ perm,
+                                                              long long r0, long long rb, double* __restrict__ out)
+{
+    const long long total = rb * n;
+    for (long long p = (long long)blockIdx.x * LP_T + threadIdx.x; p < total; p += (long long)gridDim.x * LP_T) {
+        const long long r = r0 + p / n, c = perm[p % n];
+        out[p] = r == c ? 0.0 : C[lm_condensed_index(r, c, n)];
     }
 }
 
