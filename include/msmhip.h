@@ -190,7 +190,8 @@ int msm_tica_last_img_carried(msm_tica_t* h, int* flag);
 /* What an accumulation launches -- the library's one dispatch (tica_plan, csrc/tica_plan.h), for tests to ask.
  * msm_tica_plan is pure (works with no device visible) and plans whole trajectories: geom[MSM_TICA_GEOM_INTS] is a handle's
  * geometry {F, lag, mode, T, ntiles, S32, S64, sym, ntiles_sym, sym_cohorts, sym_grid, S_sym, symw, symw_var, symw_KS, symw_S,
- * symw64, symw_S64, img_on, T2, ntile2, S_img, img_grid, have_fold, shift_on}; ptr_aligned16: bit 0 = every trajectory longer
+ * symw64, symw_S64, img_on, T2, ntile2, S_img, img_grid, have_fold, shift_on} (ntiles_sym: workgroups per cohort of the
+ * sum/difference kernel -- upper tiles, fewer when the handle packs diagonal blocks, msm_tica_sym_units); ptr_aligned16: bit 0 = every trajectory longer
  * than the lag starts on a 16-byte boundary, bit 1 = the skipped ones do too; dims_aligned4: n_features % 4 == 0 && ld % 4 == 0; fold_switch / fused_switch: the
  * values of MSM_TICA_FOLD / MSM_TICA_IMG_FUSED (-1: unset).  out[MSM_TICA_PLAN_INTS] = {path (MSM_TICA_PATH_*), flavour
  * (MSM_TICA_FL_* bits), frames per K-step, cohorts S, workgroups G, remainder cohort, frames per chunk kc, remainder workgroups,
@@ -205,6 +206,24 @@ enum { MSM_TICA_GEOM_INTS = 25, MSM_TICA_PLAN_INTS = 17 };
 int msm_tica_plan(const int* geom, int dtype_bytes, msm_idx_t ld, const msm_idx_t* n_rows, msm_idx_t n_seq, int ptr_aligned16,
                   int dims_aligned4, int fold_switch, int fused_switch, long long* out);
 int msm_tica_last_plan(msm_tica_t* h, long long* out);
+/* The units of one cohort of the sum/difference kernel for T tiles per side (csrc/tica_sym_units.h; pure, no device): a unit
+ * is one workgroup's work, MSM_TICA_SYM_UNIT_INTS ints {X column tile, Y column tile, writes the folded column sums of block X,
+ * then for each of its four waves {row panel (0 = X, 1 = Y), row offset (0 | 64), column panel, column offset, slab tile}}.
+ * pack = 0: the upper tiles in row-major order, T (T+1)/2 units; pack = 1: the diagonal tiles in groups of four give up the
+ * mirrored 64 x 64 corner nobody reads -- one tile of a group lends its three blocks to the free waves of the other three --
+ * T (T+1)/2 - T/4 units (what a handle launches when ntiles_sym of its geometry says so; MSM_TICA_SYM_PACK=0 at create: never).
+ * Writes min(units, cap) units to out (may be null with cap = 0) and returns the number of units, or a negative MSM_ERR_*. */
+enum { MSM_TICA_SYM_UNIT_INTS = 23 };
+int msm_tica_sym_units(int T, int pack, int* out, int cap);
+/* The chunk walks of a packed launch (csrc/tica_sym_units.h, tica_sym_walk; pure): chunk c holds chunk_rows[c] frames.  A
+ * cohort v of `stride` takes the chunks v, v + stride, ... and merges its fp32 accumulators when another kc frames would pass
+ * kflush, or at its end.  Either the S cohorts of the packed handle stride themselves, or -- where the fullest cohort is
+ * within 1 % of that (frames + 16 per chunk) -- the groups between two merges are those S0 UNPACKED cohorts form, dealt whole
+ * to the S cohorts, each to the lightest so far: the fp32 partials are then what they are without packing.
+ * out[cap], cap >= S + 1 + n_chunks: S + 1 offsets into the entries, then one entry per chunk: its index, bit 31 set where the
+ * cohort merges after it.  Returns 1 when the unpacked partials were kept, 0 when the cohorts stride, a negative MSM_ERR_*. */
+int msm_tica_sym_walk(const int* chunk_rows, msm_idx_t n_chunks, int S0, int S, msm_idx_t kc, msm_idx_t kflush, int* out,
+                      msm_idx_t cap);
 /* profiling: {shader-clock start, end, 100 MHz wall-clock start, end} of workgroup 0 of that launch */
 int msm_tica_debug_clocks(msm_tica_t* h, long long* out4);
 /* profiling builds (csrc built with -DMSM_TICA_PROFILE) only: out64[8 + 8*slot + i] = shader cycles wave 0 of

@@ -101,6 +101,8 @@ def _declare(lib):
     f("msm_tica_plan", C.c_int, C.POINTER(C.c_int), C.c_int, _i64, _i64p, _i64, C.c_int, C.c_int, C.c_int, C.c_int,
       C.POINTER(C.c_longlong))
     f("msm_tica_last_plan", C.c_int, _p, C.POINTER(C.c_longlong))
+    f("msm_tica_sym_units", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int)
+    f("msm_tica_sym_walk", C.c_int, C.POINTER(C.c_int), _i64, C.c_int, C.c_int, _i64, _i64, C.POINTER(C.c_int), _i64)
     f("msm_tica_allreduce", C.c_int, _p)
     f("msm_tica_counts", C.c_int, _p, _i64p, _i64p)
     f("msm_comm_rccl_available", C.c_int)

@@ -65,7 +65,14 @@ struct ChunkTable {
 struct msm_tica {
     TicaGeom g{};               // what create decided and tica_plan reads (tica_plan.h)
     int S = 0, G = 0;           // C/G slabs: S = max(S32, S64) cohorts, G = S * ntiles
-    double* slabs_sym = nullptr;                           // [S_sym * ntiles_sym][2][TM*TM]: H and D blocks
+    double* slabs_sym = nullptr;                           // [S_sym * slab_tiles()][2][TM*TM]: H and D blocks
+    int* sym_units = nullptr;   // the handle packs diagonal blocks (create_sym): [ntiles_sym] unit records of a cohort, tica_sym_units.h
+    int sym_cohorts_unpacked = 0;   // ... the cohorts it would have unpacked: their fp32 partials are kept where that is free (tica_sym_walk)
+    DevBuf walk;                    // ... the cohorts' chunk walks of the last sum/difference launch, with what they were built from
+    unsigned long long walk_key = 0;
+    long long walk_total = -1;
+    int walk_kflush = 0;
+    std::vector<int> table_rows;    // ... rows of every chunk of `table` (the walk is dealt by frames)
     // whole-matrix sum/difference kernel (tica_symw_dev.h): the variant's padded width / group width / interleave,
     // slabs [symw_S][2][FP*FP], rows in use since the last reset
     int symw_FP = 0, symw_W = 0, symw_IL = 0, symw_used = 0;
@@ -111,7 +118,9 @@ struct msm_tica {
     bool reduced = false;        // solve.A / solve.B hold the reduced matrix and the Cholesky factor of the current state
     size_t packed_len() const { return 2 * (size_t)g.F * g.F + 2 * (size_t)g.F + 2; }
     size_t colbytes() const { return (size_t)NCB * 2 * g.F * sizeof(double); }   // colpart / coltmp
-    size_t sym_slab_bytes() const { return (size_t)g.S_sym * g.ntiles_sym * 2 * TM * TM * sizeof(double); }
+    // slab tiles per cohort: the upper tiles -- g.ntiles_sym is the WORKGROUPS per cohort, fewer on a packed handle
+    int slab_tiles() const { return sym_slab_tiles(g.T); }
+    size_t sym_slab_bytes() const { return (size_t)g.S_sym * slab_tiles() * 2 * TM * TM * sizeof(double); }
 };
 
 namespace {
@@ -276,6 +285,11 @@ int main_table(Acc& a)
         int rc = h->table.upload(tab, a.key, pl.total);
         if (rc) return rc;
         h->table_img_groups = a.img_groups;
+        if (h->sym_units) {
+            h->table_rows.resize(tab.size());
+            for (size_t c = 0; c < tab.size(); ++c) h->table_rows[c] = tab[c].n;
+            h->walk_key = 0;
+        }
         if (pl.img()) {
             if (a.key) h->table_host = tab;
             a.img_tab.swap(tab);
@@ -449,7 +463,7 @@ void img_multiply_args(A& args, const Acc& a, bool x2)
     const TicaGeom& g = a.h->g;
     args.T = g.T;
     args.T2 = g.T2;
-    args.ntiles_sym = g.ntiles_sym;
+    args.ntiles_sym = a.h->slab_tiles();
     args.ntile2 = g.ntile2;
     args.S = g.S_img;
     args.main_steps = img_main_steps(args.nsteps, g.img_grid, g.ntile2);
@@ -702,12 +716,49 @@ int launch_symw(Acc& a)
     return MSM_OK;
 }
 
+// a packed handle's chunk walks (tica_sym_walk) for this launch's chunks: the last launch's when they are the same
+int sym_walk(Acc& a)
+{
+    msm_tica* h = a.h;
+    const TicaPlan& pl = a.pl;
+    if (!(a.key && h->walk_key == a.key && h->walk_total == pl.total && h->walk_kflush == pl.kflush)) {
+        std::vector<int> single;
+        if (pl.single) {
+            const long long len = a.L.n_rows[0];
+            for (long long r0 = 0; r0 < len; r0 += pl.kc) single.push_back((int)std::min<long long>(pl.kc, len - r0));
+        }
+        const std::vector<int>& rows = pl.single ? single : h->table_rows;
+        if ((long long)rows.size() != a.P.nchunks) return fail(MSM_ERR_STATE, "sum/difference launch: %lld chunks, rows of %lld", a.P.nchunks, (long long)rows.size());
+        std::vector<int> w;
+        tica_sym_walk(rows.data(), (long long)rows.size(), h->sym_cohorts_unpacked, h->g.sym_cohorts, pl.kc, pl.kflush, w);
+        h->walk_key = 0;
+        int rc = h->walk.reserve(w.size() * sizeof(int));
+        if (rc) return rc;
+        MSM_HIP_CHECK(hipMemcpyAsync(h->walk.p, w.data(), w.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+        MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `w` is pageable host memory
+        h->walk_key = a.key;
+        h->walk_total = pl.total;
+        h->walk_kflush = pl.kflush;
+    }
+    a.P.walk = static_cast<const int*>(h->walk.p);
+    return MSM_OK;
+}
+
 int launch_sym(Acc& a)
 {
     const dim3 grid(a.pl.G);
-    const TicaArgs& P = a.P;
-    switch (a.pl.flavour) {
+    TicaArgs& P = a.P;
 #define MSM_SYM_LAUNCH(...) hipLaunchKernelGGL((tica_sym_f32_kernel<__VA_ARGS__>), grid, dim3(NT), LDSSYM, stream(), P); break
+    if (a.h->sym_units) {   // a packed handle: full tiles, no remainder cohort -- the plan's flavour is folded or plain
+        P.units = a.h->sym_units;   // (P.walk: set by sym_walk ahead of the timed launch)
+        switch (a.pl.flavour) {
+            case TICA_FL_FOLD: MSM_SYM_LAUNCH(false, true, false, true);
+            case 0: MSM_SYM_LAUNCH(false, false, false, true);
+            default: return fail(MSM_ERR_STATE, "sum/difference launch: flavour %d on a packed handle", a.pl.flavour);
+        }
+        return MSM_OK;
+    }
+    switch (a.pl.flavour) {
         case TICA_FL_FOLD | TICA_FL_REM: MSM_SYM_LAUNCH(false, true, true);
         case TICA_FL_REM: MSM_SYM_LAUNCH(false, false, true);
         case TICA_FL_EDGE | TICA_FL_REM: MSM_SYM_LAUNCH(true, false, true);
@@ -809,6 +860,7 @@ int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t
     P.lag = g.lag;
     P.T = g.T;
     P.ntiles = pl.sym_slabs() ? g.ntiles_sym : g.ntiles;
+    P.slab_tiles = h->slab_tiles();
     P.S = pl.S;
     P.slabs = pl.sym_slabs() ? h->slabs_sym : h->slabs;
     P.colpart = h->coltmp;
@@ -820,6 +872,7 @@ int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t
     int rc = main_table(a);
     if (rc) return rc;
     P.n_main = pl.n_main(P.nchunks);
+    if (pl.path == TICA_SYM && h->sym_units && (rc = sym_walk(a))) return rc;
     h->last_plan = pl;
     h->last_nchunks = P.nchunks;
     h->last_super = 0;
@@ -876,8 +929,8 @@ int tica_export_queue(msm_tica* h)
                        h->packed, h->g.F);
     MSM_HIP_CHECK(hipGetLastError());
     if (h->g.sym && h->slabs_sym) {
-        hipLaunchKernelGGL(tica_export_sym_kernel, dim3((unsigned)ceil_div((size_t)h->g.ntiles_sym * TM * TM, 256)), dim3(256), 0, stream(),
-                           h->slabs_sym, h->packed, h->g.F, h->g.T, h->g.ntiles_sym, h->g.S_sym);
+        hipLaunchKernelGGL(tica_export_sym_kernel, dim3((unsigned)ceil_div((size_t)h->slab_tiles() * TM * TM, 256)), dim3(256), 0, stream(),
+                           h->slabs_sym, h->packed, h->g.F, h->g.T, h->slab_tiles(), h->g.S_sym);
         MSM_HIP_CHECK(hipGetLastError());
     }
     if (h->symw_used > 0) {
@@ -955,6 +1008,8 @@ static int create_sym(msm_tica* h)
     if ((rc = prep_kernel(tica_sym_f32_kernel<false, false, true>, NT, LDSSYM, &slots))) return rc;
     if ((rc = prep_kernel(tica_sym_f32_kernel<true, false, true>, NT, LDSSYM, &slots))) return rc;
     if ((rc = prep_kernel(tica_sym_f32_kernel<false, true, true>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, false, false, true>, NT, LDSSYM, &slots))) return rc;
+    if ((rc = prep_kernel(tica_sym_f32_kernel<false, true, false, true>, NT, LDSSYM, &slots))) return rc;
     g.sym_cohorts = slots / g.ntiles_sym;
     g.sym = g.sym_cohorts >= 1;  // at least one whole cohort resident (F <= 3968 on 256 CUs), else the C/G kernel
     // remainder cohort: the slots beyond the whole cohorts, when they are worth a launch flavour of their own --
@@ -964,6 +1019,24 @@ static int create_sym(msm_tica* h)
     const bool rem = g.sym && R * 16 >= slots && 3 * R >= g.ntiles_sym;
     g.sym_grid = rem ? slots : g.sym_cohorts * g.ntiles_sym;
     g.S_sym = g.sym_cohorts + (rem ? 1 : 0);
+    // Packed diagonal blocks (tica_sym_units.h): full tiles, no remainder cohort before or after, and only where the fewer
+    // workgroups per cohort buy a cohort -- on 512 slots F = 512 (51 -> 56 cohorts), 640 (34 -> 36), 768 (24 -> 25) and
+    // 1024 (14 -> 15).  The geometry says it through ntiles_sym (workgroups per cohort) and what follows from it; the plan
+    // does not know.  MSM_TICA_SYM_PACK=0 (read here, A/B switch of the tests and of scripts/ablate.py): never.
+    const char* pack_env = getenv("MSM_TICA_SYM_PACK");
+    const int up = sym_units_per_cohort(g.T, true), rp = slots - slots / up * up;
+    const bool rem_packed = rp * 16 >= slots && 3 * rp >= up;
+    if (g.sym && g.F % TM == 0 && !(pack_env && atoi(pack_env) == 0) && !rem && !rem_packed && slots / up > g.sym_cohorts) {
+        const std::vector<SymUnit> units = tica_sym_units(g.T, true);
+        MSM_HIP_CHECK(hipMalloc((void**)&h->sym_units, units.size() * sizeof(SymUnit)));
+        MSM_HIP_CHECK(hipMemcpyAsync(h->sym_units, units.data(), units.size() * sizeof(SymUnit), hipMemcpyHostToDevice, stream()));
+        MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `units` is pageable host memory
+        h->sym_cohorts_unpacked = g.sym_cohorts;
+        g.ntiles_sym = up;
+        g.sym_cohorts = slots / up;
+        g.sym_grid = g.sym_cohorts * up;
+        g.S_sym = g.sym_cohorts;
+    }
     return MSM_OK;
 }
 
@@ -1040,6 +1113,7 @@ int msm_tica_create(msm_tica_t** out, msm_idx_t n_features, msm_idx_t lag_time, 
     g.shift_on = 1;
     int rc = create_geometry(h);
     if (rc) {
+        if (h->sym_units) (void)hipFree(h->sym_units);
         delete h;
         return rc;
     }
@@ -1090,7 +1164,8 @@ int msm_tica_destroy(msm_tica_t* h)
     if (!h) return MSM_OK;
     (void)hipStreamSynchronize(stream());
     for (void* p : {(void*)h->slabs, (void*)h->slabs_sym, (void*)h->slabs_w, (void*)h->base, (void*)h->colpart, (void*)h->coltmp,
-                    (void*)h->packed, (void*)h->flag, (void*)h->dbg, (void*)h->cosync, (void*)h->shift, (void*)h->shsum, (void*)h->fold})
+                    (void*)h->packed, (void*)h->flag, (void*)h->dbg, (void*)h->cosync, (void*)h->shift, (void*)h->shsum, (void*)h->fold,
+                    (void*)h->sym_units})
         if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1298,6 +1373,26 @@ int msm_tica_plan(const int* geom, int dtype_bytes, msm_idx_t ld, const msm_idx_
     L.fused_switch = fused_switch;
     tica_plan_ints(tica_plan(g, L), out);
     return MSM_OK;
+}
+
+int msm_tica_sym_units(int T, int pack, int* out, int cap)
+{
+    if (T < 1 || T > 256 || cap < 0 || (cap > 0 && !out)) return fail(MSM_ERR_INVALID, "msm_tica_sym_units: bad argument");
+    const std::vector<SymUnit> units = tica_sym_units(T, pack != 0);
+    const size_t n = std::min(units.size(), (size_t)cap);
+    if (n) memcpy(out, units.data(), n * sizeof(SymUnit));
+    return (int)units.size();
+}
+
+int msm_tica_sym_walk(const int* chunk_rows, msm_idx_t n_chunks, int S0, int S, msm_idx_t kc, msm_idx_t kflush, int* out, msm_idx_t cap)
+{
+    if (n_chunks < 0 || n_chunks >= 0x7fffffff || (n_chunks > 0 && !chunk_rows) || S0 < 1 || S < 1 || kc < 1 || kflush < 1 || !out ||
+        cap < (msm_idx_t)S + 1 + n_chunks)
+        return fail(MSM_ERR_INVALID, "msm_tica_sym_walk: bad argument");
+    std::vector<int> w;
+    const bool kept = tica_sym_walk(chunk_rows, n_chunks, S0, S, kc, kflush, w);
+    std::copy(w.begin(), w.end(), out);
+    return kept ? 1 : 0;
 }
 
 int msm_tica_last_plan(msm_tica_t* h, long long* out)

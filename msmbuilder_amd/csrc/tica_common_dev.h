@@ -45,6 +45,9 @@ struct TicaArgs {
     const float* zrow;  // [F] zeros: where the dummy loads of a non-staging half-step read when the column sums are folded
     double* colA;       // sum/difference kernel with folded column sums: [S (+ 1)][F] fp64 sums of the LEFT frames, one row per cohort
     long long n_main;   // sum/difference kernel, REM: chunks [0, n_main) belong to the whole cohorts, the rest to the remainder cohort
+    int slab_tiles;     // sum/difference kernel: slab tiles per cohort, T (T + 1) / 2 (ntiles = workgroups per cohort: fewer when packed)
+    const int* units;   // packed sum/difference kernel: [ntiles] unit records of a cohort (tica_sym_units.h), else nullptr
+    const int* walk;    // ... and the cohorts' chunk walks: [S + 1 offsets][chunk index, bit 31: merge after it] (tica_sym_walk)
 };
 
 __device__ __forceinline__ TicaChunk get_chunk(const TicaArgs& P, long long c)

@@ -14,7 +14,8 @@ namespace msm {
 struct TicaGeom {
     int F, lag, mode, T, ntiles;   // T = tiles of TM features per side, ntiles = C and upper G tiles
     int S32, S64;                  // C/G kernels: resident cohorts per flavour
-    int sym, ntiles_sym, sym_cohorts, sym_grid, S_sym;   // sum/difference kernel: upper tiles, whole cohorts, workgroups of a launch
+    int sym, ntiles_sym, sym_cohorts, sym_grid, S_sym;   // sum/difference kernel: workgroups per cohort (upper tiles, fewer when the
+                                                         // handle packs diagonal blocks: tica_sym_units.h), whole cohorts, workgroups of a launch
                                                          // (sym_grid > sym_cohorts * ntiles_sym: remainder cohort), slab / column-sum rows
     int symw, symw_var, symw_KS, symw_S;   // whole-matrix kernel (fp32 mode, F <= 256): variant (SymwA ..), its K-step, workgroups of a launch
     int symw64, symw_S64;                  // ... float64 rows on the same variant (F <= 128); its resident workgroups

@@ -2,6 +2,7 @@
 // (round 5: cut out of tica.hip by kernel family, unchanged; included by it in this order)
 #pragma once
 #include "tica_cg_dev.h"
+#include "tica_sym_units.h"
 
 namespace msm {
 
@@ -78,7 +79,14 @@ __device__ __forceinline__ float __attribute__((ext_vector_type(4))) pk_sub4(flo
 // bytes and 2x the staging arithmetic of this kernel, where one staged pair of panels feeds both matrices), the MFMA wave of a
 // workgroup is alone on its SIMD with its barrier and LDS latencies, and what the interleaved kernel loses to its in-stream
 // staging (matrix pipe busy 0.87) is less than that.  The item is closed.
-template <bool PARTIAL, bool FOLD, bool REM = false>
+// PACK: the workgroups of a cohort are the units of P.units (tica_sym_units.h; full tiles, no remainder cohort): the diagonal
+// tiles of a group of four give the mirrored 64 x 64 corner nobody reads to the blocks of one of them, 9 workgroups carry a
+// cohort of F = 512 where 10 did.  Only loop-invariant values differ -- which tiles are staged as X and Y, the plane and
+// offset a wave's two fragments are read at, the slab tile and offsets its block is merged at, who writes the column sums --
+// and they are wave-uniform: the MFMA stream is the same instructions.  One thing changes in the staging: a product of an X
+// by a Y fragment gets the weight of its rows (0 past the chunk's last valid pair) from the X side alone, and a packed unit's
+// wave 3 multiplies Y by Y -- so the edge sequence of a PACK kernel weights the Y rows too.
+template <bool PARTIAL, bool FOLD, bool REM = false, bool PACK = false>
 __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -115,20 +123,37 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
     PROF_DECL;
   for (int round = 0; round < (rem ? (P.ntiles + remR - 1) / remR : 1); ++round) {   // (REM = false: one trip, folded away)
     const int cohort = rem ? P.S : p / P.ntiles;
-    const int tile = rem ? p - P.S * P.ntiles + round * remR : p % P.ntiles;  // ntiles = T (T + 1) / 2 upper tiles
+    const int tile = rem ? p - P.S * P.ntiles + round * remR : p % P.ntiles;  // ntiles = T (T + 1) / 2 upper tiles (PACK: units)
     if (rem && tile >= P.ntiles) break;
-    int I = 0, u = tile;
-    while (u >= P.T - I) {
-        u -= P.T - I;
-        ++I;
-    }
-    const int J = I + u;
-    const int I0 = I * TM, J0 = J * TM;
-
     const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
     const int kl = lane >> 5, cl = lane & 31;
-    double* slabH = P.slabs + ((size_t)cohort * P.ntiles + tile) * (2 * TM * TM);
+    // the staged column tiles X = I and Y = J; this wave's block: rows roff of panel rpan (0: the X planes, 1: the Y planes),
+    // columns coff of panel cpan, in slab tile stile; colsum: this workgroup writes the folded column sums of block I
+    int I = 0, J, rpan = 0, roff = (wave >> 1) * 64, cpan = 1, coff = (wave & 1) * 64, stile = tile;
+    bool colsum;
+    if (PACK) {
+        const SymUnit* unit = reinterpret_cast<const SymUnit*>(P.units) + tile;
+        const SymWave* w = unit->w + __builtin_amdgcn_readfirstlane(wave);
+        I = unit->X;
+        J = unit->Y;
+        colsum = unit->colsum != 0;
+        rpan = w->row_panel;
+        roff = w->row_off;
+        cpan = w->col_panel;
+        coff = w->col_off;
+        stile = w->slab_tile;
+    } else {
+        int u = tile;
+        while (u >= P.T - I) {
+            u -= P.T - I;
+            ++I;
+        }
+        J = I + u;
+        colsum = I == J;
+    }
+    const int I0 = I * TM, J0 = J * TM;
+    // (unpacked: the workgroups of a cohort ARE its slab tiles, and the kernel is the instructions it was before PACK)
+    double* slabH = P.slabs + ((size_t)cohort * (PACK ? P.slab_tiles : P.ntiles) + stile) * (2 * TM * TM);
     double* slabD = slabH + TM * TM;
 
     const int c4 = (tid & 31) * 4;
@@ -169,8 +194,12 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
         P.dbg[2] = wall_clock64();
     }
 
-    const long long c_end = REM ? (rem ? P.nchunks : P.n_main) : P.nchunks, c_step = rem ? 1 : P.S;
-    for (long long c = rem ? P.n_main : cohort; c < c_end; c += c_step) {
+    // PACK: the cohort's chunks and where it merges come from its walk (tica_sym_walk: the cohorts' own stride, or the fp32
+    // partials of the unpacked geometry dealt out whole), not from a stride and a running count of frames
+    const long long c_end = PACK ? P.walk[cohort + 1] : REM ? (rem ? P.nchunks : P.n_main) : P.nchunks, c_step = PACK ? 1 : rem ? 1 : P.S;
+    for (long long it = PACK ? P.walk[cohort] : rem ? P.n_main : cohort; it < c_end; it += c_step) {
+        const int went = PACK ? P.walk[P.S + 1 + it] : 0;
+        const long long c = PACK ? (long long)(went & 0x7fffffff) : it;
         PROF_MARK(5)
         const TicaChunk ch = get_chunk(P, c);
         const int nsteps = (ch.n + BK32 - 1) / BK32;
@@ -222,7 +251,8 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
                 const float4 wa = PARTIAL ? make_float4(sc_[j] * ma.x, sc_[j] * ma.y, sc_[j] * ma.z, sc_[j] * ma.w) \
                                           : make_float4(sc_[j], sc_[j], sc_[j], sc_[j]);               \
                 MSM_SYM_UD(xa[j], xb[j], rx_, wa, true)                                                \
-                MSM_SYM_UD(ya[j], yb[j], ry_, mb, PARTIAL)                                             \
+                /* (a product takes its row weight from the X side; PACK: wave 3 multiplies Y by Y) */ \
+                MSM_SYM_UD(ya[j], yb[j], ry_, (PACK ? wa : mb), PACK || PARTIAL)                       \
             }                                                                                          \
             MSM_STORE_X(BUF)                                                                           \
             MSM_STORE_Y(BUF)                                                                           \
@@ -230,8 +260,8 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
 #define MSM_SYM_FRAGS(BUF, KK)                                                                         \
                     const f2v npu = MSM_F2((BUF) * 4 * PAN + 0 * PAN + (KK) * 2 * TM + fa),            \
                               npd = MSM_F2((BUF) * 4 * PAN + 1 * PAN + (KK) * 2 * TM + fa),            \
-                              nqu = MSM_F2((BUF) * 4 * PAN + 2 * PAN + (KK) * 2 * TM + fb),            \
-                              nqd = MSM_F2((BUF) * 4 * PAN + 3 * PAN + (KK) * 2 * TM + fb);
+                              nqu = MSM_F2((BUF) * 4 * PAN + 0 * PAN + (KK) * 2 * TM + fb),            \
+                              nqd = MSM_F2((BUF) * 4 * PAN + 1 * PAN + (KK) * 2 * TM + fb);
 #define MSM_SYM_MFMAS                                                                                  \
                     __builtin_amdgcn_sched_barrier(0);                                                 \
                     aH[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(pu.x, qu.x, aH[0][0], 0, 0, 0);    \
@@ -256,7 +286,8 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
         }
         __syncthreads();
         PROF_MARK(0)
-        const int fa = kl * TM + wr * 64 + 2 * cl, fb = kl * TM + wc * 64 + 2 * cl;  // floats
+        // floats; fa and fb carry the base of their u plane (X: 0, Y: 2 PAN), the d plane is PAN = 8 KiB behind it
+        const int fa = rpan * 2 * PAN + kl * TM + roff + 2 * cl, fb = cpan * 2 * PAN + kl * TM + coff + 2 * cl;
         for (int s = 0; s < nsteps; ++s) {
 #pragma unroll
             for (int b = 0; b < 2; ++b) {  // half-step h = 2 s + b reads buffer b and fills buffer b ^ 1 with h + 1
@@ -272,7 +303,7 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
                 const global_ptr<char> pa = FOLD && !fast ? zb : cx.base + kb, pb = FOLD && !fast ? zb : cx.baseB + kb;
                 const unsigned ox = fast ? offx : ca, oy = fast ? offy : cb;
                 f2v pu = MSM_F2(b * 4 * PAN + 0 * PAN + fa), pd = MSM_F2(b * 4 * PAN + 1 * PAN + fa);
-                f2v qu = MSM_F2(b * 4 * PAN + 2 * PAN + fb), qd = MSM_F2(b * 4 * PAN + 3 * PAN + fb);
+                f2v qu = MSM_F2(b * 4 * PAN + 0 * PAN + fb), qd = MSM_F2(b * 4 * PAN + 1 * PAN + fb);
                 f4v rsh;
                 PROF_MARK(1)
 #pragma unroll
@@ -328,11 +359,16 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
             if (tid == 0) __hip_atomic_fetch_add(P.cosync + cohort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         rows_acc += ch.n;
-        if (rows_acc + P.kc > P.kflush || c + c_step >= c_end) {
+        if (PACK ? went < 0 : (rows_acc + P.kc > P.kflush || c + c_step >= c_end)) {
             rows_acc = 0;
-            // accumulator register r of block (bi, bj), lane (kl, cl) = tile row wr*64 + 2*rho + bi with
-            // rho = (r & 3) + 8 (r >> 2) + 4 kl, tile column wc*64 + 2*cl + bj: the two bj of a lane are adjacent doubles
-            unsigned toff = (unsigned)((wr * 64 + 8 * kl) * TM + wc * 64 + 2 * cl);
+            // accumulator register r of block (bi, bj), lane (kl, cl) = tile row roff + 2*rho + bi with
+            // rho = (r & 3) + 8 (r >> 2) + 4 kl, tile column coff + 2*cl + bj: the two bj of a lane are adjacent doubles
+            // (PACK: formed here from the thread index, behind a barrier the optimiser cannot see through -- hoisted out of the
+            //  chunk loop it is one register too many for the folded variant)
+            unsigned tl = (unsigned)tid;
+            if (PACK) asm volatile("" : "+v"(tl));
+            unsigned toff = PACK ? (unsigned)((roff + 8 * (int)((tl >> 5) & 1)) * TM + coff + 2 * (int)(tl & 31))
+                                 : (unsigned)((roff + 8 * kl) * TM + coff + 2 * cl);
             asm volatile("" : "+v"(toff));
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -367,7 +403,7 @@ __global__ __launch_bounds__(NT, 2) void tica_sym_f32_kernel(TicaArgs P)
         cs[2 * NT + tid] = cs2;
         cs[3 * NT + tid] = cs3;
         __syncthreads();
-        if (I == J && tid < TM) {  // column tid of the block = element tid & 3 of the threads (srow, tid >> 2), srow = 0..7
+        if (colsum && tid < TM) {  // column tid of the block = element tid & 3 of the threads (srow, tid >> 2), srow = 0..7
             double a = 0.0;
 #pragma unroll
             for (int r = 0; r < 8; ++r) a += cs[(tid & 3) * NT + r * 32 + (tid >> 2)];
