@@ -1008,6 +1008,33 @@ int msm_transmat_mle(const double* C, msm_idx_t n, double prior, msm_idx_t max_i
 int msm_mle_last_stats(msm_idx_t* out3);
 int msm_syev_top(const double* S, msm_idx_t n, msm_idx_t k, double* evals, double* evecs, int on_device);
 
+/* ------------------------------------------------------------------------------------------
+ * Sparse generalized eigenpairs (SparseTICA; decomposition/_speigh.pyx of msmbuilder): an approximate
+ * solution of  max x^T A x - rho |x|_0  s.t. x^T B x <= 1  by majorisation-minimisation around an ADMM solve, all float64,
+ * outer and inner loops in ONE persistent launch (relaunched every MSM_SPEIGH_BUDGET ADMM iterations with bit-identical
+ * results; MSM_SPEIGH_GRID picks the layout).  1 <= n <= 2048.  on_device: every ARRAY argument is a device pointer (1) or a
+ * host pointer (0); u and info are always host.  evals / evecs describe B = sum_j evals[j] e_j e_j^T with evecs[j * n + i] =
+ * component i of e_j (msm_syev_top's layout).
+ * msm_speigh_project: out = the point of { z : z^T B z <= 1 } nearest to a (a itself, bit for bit, when a lies inside).
+ * msm_speigh_admm: min 1/2 |x - b|^2 + |D(w) x|_1 s.t. x^T B x <= 1, warm-started at x_inout, which receives the
+ *   soft-thresholded iterate (its exact zeros are the sparsity pattern).  info (host, 4 doubles): iterations, launches,
+ *   status (0 converged, 1 maxiter), final penalty parameter.
+ * msm_speigh: the pair.  x0 (or NULL: the top generalized eigenvector from msm_sygv_top), evalsB / evecsB (both or neither;
+ *   NULL: msm_syev_top of B).  *u = the pseudo-eigenvalue, v[n] = the sparse vector (v^T B v = 1, sum(v) >= 0, no negative
+ *   zeros), x_out (or NULL) = the iterate before renormalisation.  info (host, 8 doubles): outer steps (ADMM solves), ADMM
+ *   iterations, launches, last objective, nonzeros, status (0 converged, 1 maxiter), workgroups (0: single-workgroup
+ *   layout), tau.  MSM_ERR_INVALID: null pointers, n, rho < 0, eps <= 0, tol <= 0, maxiter < 1 (before any device work),
+ *   B not positive definite (LAPACK's text); MSM_ERR_NONFINITE: NaN / Inf in A or B; MSM_ERR_STATE: the grid barrier of the
+ *   launch timed out (bounded wait).
+ * msm_scdeflate: out = A - (A x)(x^T A)^T / (x^T A x), the two products kept apart (A need not be symmetric to rounding
+ *   after a deflation); out may be A on the device. */
+int msm_speigh_project(const double* a, const double* evals, const double* evecs, msm_idx_t n, double* out, int on_device);
+int msm_speigh_admm(const double* b, const double* w, const double* evals, const double* evecs, double* x_inout, msm_idx_t n,
+                    double tol, msm_idx_t maxiter, double* info, int on_device);
+int msm_speigh(const double* A, const double* B, msm_idx_t n, double rho, double eps, double tol, msm_idx_t maxiter, const double* x0,
+               const double* evalsB, const double* evecsB, double* u, double* v, double* x_out, double* info, int on_device);
+int msm_scdeflate(const double* A, const double* x, msm_idx_t n, double* out, int on_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ from . import libdistance  # noqa: F401
 from . import preprocessing  # noqa: F401
 from .cluster import (KCenters, KMeans, KMedoids, LandmarkAgglomerative, MiniBatchKMeans, MiniBatchKMedoids,  # noqa: F401
                       RegularSpatial)
-from .decomposition import KernelTICA, LandmarkNystroem, Nystroem, tICA  # noqa: F401
+from .decomposition import KernelTICA, LandmarkNystroem, Nystroem, SparseTICA, tICA  # noqa: F401
 from .hmm import GaussianHMM, VonMisesHMM  # noqa: F401
 from .lumping import MVCA  # noqa: F401
 from .msm import MarkovStateModel  # noqa: F401

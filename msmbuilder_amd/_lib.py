@@ -195,6 +195,10 @@ def _declare(lib):
     f("msm_colstats", C.c_int, C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _i64, C.c_int, _p, C.POINTER(C.c_int))
     f("msm_col_digit_hist", C.c_int, C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _i64, _p, C.c_int, C.c_int, C.c_int, _p)
     f("msm_scale_apply", C.c_int, _p, C.c_int, _i64, _i64, _i64, _p, _p, C.c_int, _p, _i64, C.c_int)
+    f("msm_speigh_project", C.c_int, _p, _p, _p, _i64, _p, C.c_int)
+    f("msm_speigh_admm", C.c_int, _p, _p, _p, _p, _p, _i64, C.c_double, _i64, _f64p, C.c_int)
+    f("msm_speigh", C.c_int, _p, _p, _i64, C.c_double, C.c_double, C.c_double, _i64, _p, _p, _p, _f64p, _p, _p, _f64p, C.c_int)
+    f("msm_scdeflate", C.c_int, _p, _p, _i64, _p, C.c_int)
     f("msm_ts_filter", C.c_int, C.POINTER(_p), C.POINTER(_p), _i64p, _i64, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int,
       _p, _p, _p, _i64, C.c_double, C.c_int, _i64, _i64)
 

@@ -2,5 +2,6 @@
 from .tica import tICA
 from .kernel_approximation import Nystroem, LandmarkNystroem
 from .ktica import KernelTICA
+from .sparsetica import SparseTICA
 
-__all__ = ['tICA', 'KernelTICA', 'Nystroem', 'LandmarkNystroem']
+__all__ = ['tICA', 'KernelTICA', 'SparseTICA', 'Nystroem', 'LandmarkNystroem']
