@@ -33,6 +33,7 @@
  *                     all pairs) and :248-273 (predict: cdist + pooling per cluster)
  *   msm_divergence_*  utils/divergence.py:14-72 (the nested loops over rows and columns), as MVCA (lumping/mvca.py) runs them
  *                     through cluster/agglomerative.py:50-69
+ *   msm_bace_*        lumping/bace.py:228-327 (the Bayes factors of all connected pairs and the merge loop)
  *   msm_kmeans_* / msm_mbk_*  sklearn MiniBatchKMeans arithmetic behind
  *                     cluster/__init__.py:67-69 (third-party)
  * The exact reference signatures of libdistance are additionally exported,
@@ -641,6 +642,36 @@ int msm_divergence_rows_f32(const float* P, const float* Q, msm_idx_t n, msm_idx
 int msm_divergence_rows_f64(const double* P, const double* Q, msm_idx_t n, msm_idx_t m, const char* kind, double* out);
 int msm_divergence_plan(msm_idx_t* out4);
 int msm_divergence_log_probe(const double* x, msm_idx_t n, int reps, double* out, float* ms);
+
+/* ---- BACE lumping (lumping/bace.py): Bayes factors between the rows of a count matrix and the merge loop ---------------
+ * counts: n x n float64, row-major, non-negative and finite; w: n weights (positive and finite for every kept state);
+ * the flags are int32, one per state.  w and the flags are HOST arrays; counts (and out, d_out) follow on_device.  Over the
+ * columns k of the kept states, ascending, in float64:
+ *     c1_k = counts[i, k] + (unmerged[i] && unmerged[k] ? 1 / n : 0),  p1_k = c1_k / w[i]      (likewise c2, p2 for j)
+ *     cp_k = (c1_k + c2_k) / (w[i] + w[j]),   d = sum_k c1_k log(p1_k / cp_k) + sum_k c2_k log(p2_k / cp_k)
+ * and the value stored for the pair is float32(1 / float32(d)), both correctly rounded.  One thread adds a pair's terms in
+ * ascending k, in the tile kernel and in the row kernel alike: a pair has the same bits from both, and (i, j) == (j, i).
+ *   msm_bace_pairs: row < 0: out[i, j] for i < j, both kept, counts[i, j] > 1 (the tile kernel); row >= 0: out[row, j] for
+ *     every kept j != row with counts[row, j] > 1 (the row kernel).  Every other entry of out (n x n float32) is 0.  d_out
+ *     (nullable, n x n float64) receives d itself at the same places.
+ *   msm_bace_fit: keep marks the states that take part (all unmerged).  Computes the matrix, then merges
+ *     max(kept - n_macrostates, 0) times: the first maximum of the matrix in row-major order (an inf counts) names (x, y); y
+ *     is merged into x as the reference's _mergeTwoClosestStates does it; row x is evaluated again.  The loop is queued on
+ *     the stream and nothing is read back until it ends.  merges[2 s], merges[2 s + 1], values[s] are the selection after s
+ *     merges, the look-ahead after the last merge included: *n_records = merges + 1 <= capacity.  A selection that finds no
+ *     positive entry is recorded as (-1, -1, 0) and ends the loop (so are all later ones).  ms3 (nullable): the times of the
+ *     initial matrix, of the loop and of both in milliseconds.  The caller's counts are not changed.
+ *   msm_bace_plan: out6 = {tile rows = tile columns, columns per LDS chunk of the tile kernel, pairs per workgroup and
+ *     columns per pass of the row kernel, threads per workgroup, the largest n}.
+ * The environment variable MSM_BACE_MAX_GRID (read at every call) caps the workgroups of the grid-stride kernels; it is
+ * there for the tests and changes no result.
+ * MSM_ERR_INVALID: null pointers, n < 2, n > 16384, n_macrostates < 1, no kept state, a bad weight, row not kept, capacity too small;
+ * MSM_ERR_NONFINITE: a negative or non-finite count. */
+int msm_bace_pairs(const double* counts, const double* w, const int32_t* unmerged, const int32_t* alive, msm_idx_t n, msm_idx_t row,
+                   float* out, double* d_out, int on_device);
+int msm_bace_fit(const double* counts, const double* w, const int32_t* keep, msm_idx_t n, msm_idx_t n_macrostates, int32_t* merges,
+                 float* values, msm_idx_t capacity, msm_idx_t* n_records, float* ms3, int on_device);
+int msm_bace_plan(msm_idx_t* out6);
 
 /* ---- Nystroem kernel feature map (decomposition/kernel_approximation.py, ktica.py) ------------------------------------
  * out[i, :] = k(rows[i], landmarks) . B - c     (rows: n x n_features at row stride ld elements; landmarks: L x

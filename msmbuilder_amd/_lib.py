@@ -156,6 +156,9 @@ def _declare(lib):
         f("msm_divergence_rows_" + sfx, C.c_int, _p, _p, _i64, _i64, C.c_char_p, _p)
     f("msm_divergence_plan", C.c_int, _i64p)
     f("msm_divergence_log_probe", C.c_int, _p, _i64, C.c_int, _p, C.POINTER(C.c_float))
+    f("msm_bace_pairs", C.c_int, _p, _p, _p, _p, _i64, _i64, _p, _p, C.c_int)
+    f("msm_bace_fit", C.c_int, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64p, _p, C.c_int)
+    f("msm_bace_plan", C.c_int, _i64p)
     f("msm_kernel_map_plan", C.c_int, _i64, _i64, _i64, C.c_int, _i64p)
     for sfx in ("f32", "f64"):
         f("msm_kernel_map_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, C.c_int, C.c_double, C.c_double,
