@@ -76,19 +76,6 @@ struct KcbState {
 // (levels below 0.91 were tried in round 4 -- twelve levels down to 0.58: the number of rounds did not move, 19 on the bench's
 //  projection at 10M and at 1.25M rows: what ends a round is the list's capacity, not the threshold's rate of descent -- and
 //  the extra level counters cost 15 % of a fit)
-// Rounds the host queues before it looks at the progress counter again.  A synchronisation costs 35-50 us of idle GPU, an
-// empty round (all K centres fixed: three early-returning launches) about 14: so the first group aims at the whole fit at
-// a typical 12 centres per round, and the later ones at what is left at the rate seen so far, plus one.  The value depends
-// on nothing but K and the counter, which every rank of a sharded fit holds identically.
-static int kcb_group(int K, int done, int rounds_so_far, int done_at_start)
-{
-    const int left = K - done;
-    if (left <= 0) return 0;
-    int per = 12;
-    if (rounds_so_far > 0) per = std::max(1, (done - done_at_start) / rounds_so_far);
-    const int g = (left + per - 1) / per + (rounds_so_far > 0 ? 1 : 0);
-    return std::min(std::max(g, 1), 24);
-}
 
 // the state before the first round: `k_done` centres fixed by the plain passes, no list yet.  (A launch instead of a copy
 // from the host's stack and the synchronisation that keeps the stack alive: 20-30 us per fit.)

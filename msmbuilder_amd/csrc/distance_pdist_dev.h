@@ -1,4 +1,4 @@
-// distance_pdist_dev.h -- pdist_kernel, sumdist_kernel, sum_partial_kernel
+// distance_pdist_dev.h -- pdist_kernel and sumdist_kernel
 // (round 5: cut out of distance.hip by kernel family, unchanged; included by it in this order)
 #pragma once
 #include "common.h"
@@ -71,22 +71,6 @@ __global__ __launch_bounds__(DT) void sumdist_kernel(PdArgs P)
         __syncthreads();
     }
     if (threadIdx.x == 0) P.partial[blockIdx.x] = red[0];
-}
-
-// deterministic per-block fp64 sums of a vector (inertia = np.sum(distances_))
-__global__ __launch_bounds__(DT) void sum_partial_kernel(const double* __restrict__ v, long long n,
-                                                         double* __restrict__ partial)
-{
-    __shared__ double red[DT];
-    double s = 0.0;
-    for (long long i = (long long)blockIdx.x * DT + threadIdx.x; i < n; i += (long long)gridDim.x * DT) s += v[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = DT / 2; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
 }  // namespace msm

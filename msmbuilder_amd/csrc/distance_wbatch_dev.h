@@ -1,4 +1,4 @@
-// distance_wbatch_dev.h -- kwb_* kernels: SEVERAL centres per screened pass of wide rows (round 6; included by distance.hip
+// distance_wbatch_dev.h -- kwb_* kernels: SEVERAL centres per screened pass of wide rows (round 6; included by kcenters.hip
 // after distance_wscreen_dev.h and distance_kcbatch_dev.h).
 //
 // The screened passes of distance_wscreen_dev.h cost m + 8 bytes per row -- but one pass per centre: KCenters(200) on

@@ -1,5 +1,5 @@
 // distance_wscreen_dev.h -- k-centers passes of WIDE rows (and of any float32 rows) screened on a feature-major byte copy.
-// (round 6; included by distance.hip after distance_screen_dev.h)
+// (round 6; included by kcenters.hip after distance_screen_dev.h)
 //
 // What was there: the screened passes of rounds 2-5 (distance_screen_dev.h, distance_kcbatch_dev.h) keep a row's byte copy in
 // a thread's registers and exist for float64 rows of <= 16 features.  Everything else took one PLAIN pass per centre over the

@@ -1,4 +1,4 @@
-"""K-centers pass chains at the sizes where their grids differ (csrc/distance.hip kcenters_impl).
+"""K-centers pass chains at the sizes where their grids differ (csrc/kcenters.hip kcenters_impl).
 
 Every pass of a fit writes one KcPartial (best distance, row) per workgroup into one of two arrays of the partials
 buffer, and the next pass reads all of them to choose its centre.  The passes run on grids of different sizes (DT = 256

@@ -1,4 +1,4 @@
-"""The row-sharded k-centers fit, msm_kcenters_fit_sharded_f32/_f64 (csrc/distance.hip kcenters_fit_sharded_impl): what
+"""The row-sharded k-centers fit, msm_kcenters_fit_sharded_f32/_f64 (csrc/kcenters.hip kcenters_fit_sharded_impl): what
 every multi-GPU run of KCenters executes and what bench.py times through KCenters._force_sharded in a world of one.
 
 The three loops of the sharded fit and what selects them (FC = 32 float32 / 16 float64 features, the register path):
