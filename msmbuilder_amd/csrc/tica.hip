@@ -24,104 +24,20 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
+#include <functional>
 #include <vector>
 
 #include "tica_plan.h"         // TicaGeom / TicaLaunch / TicaPlan and tica_plan: which kernel a launch takes, decided once
 #include "tica_common_dev.h"   // constants, chunk / argument structs and block-id helpers shared by the tICA kernels
-#include <functional>
-
+#include "tica_handle.h"       // ChunkTable, struct msm_tica; tica_export_queue, which tica_solve.hip calls
 #include "tica_cg_dev.h"   // staging helpers (ChunkCtx, Stage32) and tica_mfma_f32_kernel, the fp32 C/G kernel
 #include "tica_sym_dev.h"   // tica_sym_f32_kernel (sum/difference form, the bench kernel) and tica_export_sym_kernel
 #include "tica_symw_dev.h"   // tica_symw_f32_kernel (sum/difference form for F <= 256: a workgroup owns all of H and D) and its export
 #include "tica_f64_dev.h"   // tica_mfma_f64_kernel (fp64 MFMA)
 #include "tica_img_pack_dev.h"   // tica_img_kernel (packing pre-pass of the bf16 image path) and tica_img_steps_kernel
 #include "tica_colsum_dev.h"   // column sums, folded sums, mean shift and export kernels
-#include "tica_project_dev.h"   // tica_project_kernel / tica_project_mfma_kernel (transform)
-#include "tica_solve_dev.h"   // finalise / RBLW / shrink / top-pairs kernels of the device-resident solve
 
 using namespace msm;
-
-// a chunk table on the device, with the key of what it was built from
-struct ChunkTable {
-    DevBuf buf;
-    unsigned long long key = 0;   // 0: not to be found again
-    long long total = -1, n = 0;  // frames of the keyed launch (a second guard), chunks
-    bool hit(unsigned long long k, long long t) const { return k != 0 && key == k && total == t; }
-    const TicaChunk* chunks() const { return static_cast<const TicaChunk*>(buf.p); }
-    int upload(const std::vector<TicaChunk>& tab, unsigned long long k, long long t)
-    {
-        key = 0;
-        int rc = buf.reserve(tab.size() * sizeof(TicaChunk));
-        if (rc) return rc;
-        MSM_HIP_CHECK(hipMemcpyAsync(buf.p, tab.data(), tab.size() * sizeof(TicaChunk), hipMemcpyHostToDevice, stream()));
-        MSM_HIP_CHECK(hipStreamSynchronize(stream()));  // `tab` is pageable host memory
-        key = k;
-        total = t;
-        n = (long long)tab.size();
-        return MSM_OK;
-    }
-};
-
-struct msm_tica {
-    TicaGeom g{};               // what create decided and tica_plan reads (tica_plan.h)
-    int S = 0, G = 0;           // C/G slabs: S = max(S32, S64) cohorts, G = S * ntiles
-    double* slabs_sym = nullptr;                           // [S_sym * slab_tiles()][2][TM*TM]: H and D blocks
-    int* sym_units = nullptr;   // the handle packs diagonal blocks (create_sym): [ntiles_sym] unit records of a cohort, tica_sym_units.h
-    int sym_cohorts_unpacked = 0;   // ... the cohorts it would have unpacked: their fp32 partials are kept where that is free (tica_sym_walk)
-    DevBuf walk;                    // ... the cohorts' chunk walks of the last sum/difference launch, with what they were built from
-    unsigned long long walk_key = 0;
-    long long walk_total = -1;
-    int walk_kflush = 0;
-    std::vector<int> table_rows;    // ... rows of every chunk of `table` (the walk is dealt by frames)
-    // whole-matrix sum/difference kernel (tica_symw_dev.h): the variant's padded width / group width / interleave,
-    // slabs [symw_S][2][FP*FP], rows in use since the last reset
-    int symw_FP = 0, symw_W = 0, symw_IL = 0, symw_used = 0;
-    double* slabs_w = nullptr;
-    double* slabs = nullptr;    // [G][TM*TM]
-    double* base = nullptr;     // packed [2FF+2F] imported state
-    double* colpart = nullptr;  // [NCB][2][F]
-    double* coltmp = nullptr;   // [NCB][2][F]
-    double* packed = nullptr;   // [2FF+2F+2] export scratch
-    int* flag = nullptr;        // [2]: [0] sticky, [1] per-call
-    long long* dbg = nullptr;   // [4] profiling clocks
-    unsigned* cosync = nullptr; // [S] cohort pacing counters
-    float* shift = nullptr;     // [F] reference row r of the mean shift (fp32 / bf16 kernels); valid once have_shift
-    double* shsum = nullptr;    // [3F] raw column sums [A | B | W] of everything accumulated under the shift
-    bool have_shift = false;
-    double* fold = nullptr;     // folded column sums: [S_sym][F] per-cohort sums of the left frames | [FOLD_NB][F] sample partials | [F] zeros
-    bool last_folded = false;   // the most recent launch took the folded path
-    bool cg_dirty = false;      // the C/G slabs (`slabs`) hold something since the last reset: only then does the export sum them
-    bool slabs_dirty = false;   // slabs_sym hold something since the last reset (a rejected folded launch must be able to undo itself)
-    DevBuf snap;                // ... from this copy
-    DevBuf foldimg;             // bf16 image path: [nchunks][F] per-chunk sums of the left frames
-    DevBuf imgsteps;            // fused bf16 kernel / carried pack: the launch's K-step records (tica_img_steps_kernel)
-    DevBuf colsteps;            // carried pack: [pack steps of a super-chunk][Fp] fp64 column sums of the left frames
-    int last_carried = 0;       // the last accumulate packed its later super-chunks inside the multiply (msm_tica_last_img_carried)
-    int last_fused = 0;         // the last accumulate ran the fused kernel (msm_tica_last_img_fused)
-    TicaPlan last_plan;         // the plan of the last accumulate, its chunks and (image ring) super-chunks (msm_tica_last_plan)
-    long long last_nchunks = 0, last_super = 0;
-    long long n_sh = 0, nw_sh = 0;  // shifted pairs, and the total weight of their Gram terms (2 n_sh for whole trajectories)
-    long long n_obs = 0, n_seq = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the most recent MFMA launch (bf16 image path: the whole pack + multiply pipeline)
-    bool timed = false;
-    // The chunk tables of the last launch stay on the device with a key of what they were built from.  Fitting the
-    // SAME trajectories again (the bench's steps, partial_fit loops, cross-validated re-fits through a pooled handle) then
-    // skips the table build, its upload and the two stream synchronisations that cover the pageable host vectors: ~0.3 ms
-    // of idle GPU at 1,000 trajectories, and the host gets to the MFMA launch that much earlier.
-    ChunkTable table, table2;   // the launch's chunks; boundary rows (folded sums) or right frames (segments)
-    long long table_img_groups = 0;
-    std::vector<TicaChunk> table_host;   // bf16 image path: the super-chunk loop walks the table on the host
-    DevBuf staging;
-    double* solve_pin = nullptr; // pinned host staging of the solve's results (one device-to-host copy per solve)
-    size_t solve_pin_n = 0;
-    DevBuf solve;                // device-resident solve: [A (F*F) | B (F*F) | mu F | D F | E F | scal 4 | part 2*nblk | scale F | Y k*F | vals F | ints]
-    bool reduced = false;        // solve.A / solve.B hold the reduced matrix and the Cholesky factor of the current state
-    size_t packed_len() const { return 2 * (size_t)g.F * g.F + 2 * (size_t)g.F + 2; }
-    size_t colbytes() const { return (size_t)NCB * 2 * g.F * sizeof(double); }   // colpart / coltmp
-    // slab tiles per cohort: the upper tiles -- g.ntiles_sym is the WORKGROUPS per cohort, fewer on a packed handle
-    int slab_tiles() const { return sym_slab_tiles(g.T); }
-    size_t sym_slab_bytes() const { return (size_t)g.S_sym * slab_tiles() * 2 * TM * TM * sizeof(double); }
-};
 
 namespace {
 
@@ -919,8 +835,10 @@ int tica_accumulate_device(msm_tica* h, const void* const* ptrs, const msm_idx_t
     return MSM_OK;
 }
 
-// queues slabs / column partials / base -> h->packed (raw moments, un-shifted); no synchronisation
-int tica_export_queue(msm_tica* h)
+}  // namespace
+
+// queues slabs / column partials / base -> h->packed (raw moments, un-shifted); no synchronisation (tica_handle.h)
+int msm::tica_export_queue(msm_tica* h)
 {
     const size_t total = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
     hipLaunchKernelGGL(tica_export_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream(),
@@ -947,13 +865,13 @@ int tica_export_queue(msm_tica* h)
     return MSM_OK;
 }
 
+namespace {
+
 int tica_export_device(msm_tica* h)
 {
     const size_t total = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
-    {
-        const int rcq = tica_export_queue(h);
-        if (rcq) return rcq;
-    }
+    const int rcq = tica_export_queue(h);
+    if (rcq) return rcq;
     const double cnt[2] = {(double)h->n_obs, (double)h->n_seq};
     MSM_HIP_CHECK(hipMemcpyAsync(h->packed + total, cnt, sizeof(cnt), hipMemcpyHostToDevice, stream()));
     MSM_HIP_CHECK(hipStreamSynchronize(stream()));
@@ -1454,8 +1372,6 @@ int msm_tica_import_packed(msm_tica_t* h, const double* buf, int on_device)
 {
     if (!h || !buf) return fail(MSM_ERR_STATE, "null argument");
     const size_t FF2 = 2 * (size_t)h->g.F * h->g.F + 2 * (size_t)h->g.F;
-    long long keep_flag = 0;
-    (void)keep_flag;
     int rc = tica_zero(h);
     if (rc) return rc;
     MSM_HIP_CHECK(hipMemcpyAsync(h->base, buf, FF2 * sizeof(double),
@@ -1503,286 +1419,6 @@ int msm_tica_import(msm_tica_t* h, const double* C, const double* G, const doubl
     return MSM_OK;
 }
 
-}  // extern "C"
-
-// ---- device-resident finalise + solve ------------------------------------------------------------------------
-namespace {
-
-struct SolveBufs {
-    double *A, *B, *mu, *D, *E, *scal, *part, *scale, *Y, *vals, *trdw;
-    double *Winv, *T;             // U^-T of the factorisation (n <= 1024: reduction by GEMMs, back-transformation by a thin product), GEMM scratch
-    double* sswork;               // subspace iteration workspace (subspace.hip)
-    double *lam, *S, *Yk, *res;   // top-k tail (toppairs.hip): eigenvalues [64], back-transformed vectors [64][F], reduced vectors [64][F], checks [320]
-    int* ints;  // [0..1] non-finite flags (OC, S), [2] potrf info, [3] syevd info; [8 ..] sytrd barrier flags + status
-    int nblk;
-};
-
-int solve_bufs(msm_tica* h, SolveBufs* b)
-{
-    const size_t F = (size_t)h->g.F, FF = F * F;
-    const int nblk = (int)ceil_div((int64_t)FF, 256);
-    const size_t nd = 5 * FF + 13 * F + 4 + 2 * (size_t)nblk + 384 + 128 * F + subspace_work_doubles((int)F);
-    int rc = h->solve.reserve(nd * sizeof(double) + (8 + F / 16 + 4) * sizeof(int));
-    if (rc) return rc;
-    double* p = h->solve.as<double>();
-    b->A = p;
-    b->B = b->A + FF;
-    b->Y = b->B + FF;
-    b->mu = b->Y + FF;
-    b->D = b->mu + F;
-    b->E = b->D + F;
-    b->scale = b->E + F;
-    b->vals = b->scale + F;
-    b->scal = b->vals + F;
-    b->part = b->scal + 4;
-    b->trdw = b->part + 2 * (size_t)nblk;   // 8F doubles of sytrd exchange records
-    b->lam = b->trdw + 8 * F;
-    b->res = b->lam + 64;
-    b->S = b->res + 320;   // res: 2k + k^2 doubles, k <= 16
-    b->Yk = b->S + 64 * F;
-    b->sswork = b->Yk + 64 * F;
-    b->Winv = b->sswork + subspace_work_doubles((int)F);
-    b->T = b->Winv + FF;
-    b->ints = reinterpret_cast<int*>(b->T + FF);
-    b->nblk = nblk;
-    return MSM_OK;
-}
-
-// export -> finalise -> shrink -> B = L L^T -> A <- L^-1 A L^-T, all queued on the stream (no synchronisation)
-int tica_reduce_device(msm_tica* h, double shrinkage, long long n_rblw, const double* scale_host, SolveBufs* b)
-{
-    int rc = solve_bufs(h, b);
-    if (rc) return rc;
-    const long long npairs = h->n_obs - (long long)h->g.lag * h->n_seq;
-    if (h->n_obs <= 0 || npairs <= 0) return fail(MSM_ERR_STATE, "the model must be fit() before use");
-    // the packed raw moments (slab sums, un-shifted) stay on the device
-    if ((rc = tica_export_queue(h))) return rc;
-    MSM_HIP_CHECK(hipGetLastError());
-    MSM_HIP_CHECK(hipMemsetAsync(b->ints, 0, 8 * sizeof(int), stream()));
-    if (scale_host) MSM_HIP_CHECK(hipMemcpyAsync(b->scale, scale_host, h->g.F * sizeof(double), hipMemcpyHostToDevice, stream()));
-    hipLaunchKernelGGL(tica_finalise_kernel, dim3((unsigned)b->nblk), dim3(256), 0, stream(), h->packed,
-                       scale_host ? b->scale : (const double*)nullptr, 2.0 * (double)npairs, h->g.F, b->A, b->B, b->mu, b->part, b->ints);
-    hipLaunchKernelGGL(tica_rblw_kernel, dim3(1), dim3(256), 0, stream(), b->part, b->nblk, shrinkage, (double)n_rblw, h->g.F, b->scal);
-    hipLaunchKernelGGL(tica_shrink_kernel, dim3((unsigned)b->nblk), dim3(256), 0, stream(), b->B, b->scal, h->g.F);
-    MSM_HIP_CHECK(hipGetLastError());
-    if ((rc = sygv_reduce_device(b->A, b->B, h->g.F, b->ints + 2, b->Winv, b->T))) return rc;
-    h->reduced = true;
-    return MSM_OK;
-}
-
-// status of the queued reduction, after the stream was synchronised: info = {rho, tr S, flags...}
-int tica_reduce_status(const double scal[4], const int ints[8], double* info)
-{
-    if (info) {
-        info[0] = scal[0];
-        info[1] = scal[1];
-        info[2] = (double)ints[2];
-        info[3] = (double)ints[3];
-        info[4] = (double)ints[0];
-        info[5] = (double)ints[1];
-    }
-    if (ints[0]) return fail(MSM_ERR_NONFINITE, "offset correlation matrix is not symmetric");
-    if (ints[1]) return fail(MSM_ERR_NONFINITE, "correlation matrix is not symmetric");
-    if (ints[2] != 0)
-        return fail(MSM_ERR_INVALID, "The leading minor of order %d of B is not positive definite. The factorization of B "
-                    "could not be completed and no eigenvalues or eigenvectors were computed.", ints[2]);
-    return MSM_OK;
-}
-
-// the results of a top-k solve gathered into ONE buffer for one device-to-host copy (seven small copies into pageable host
-// arrays cost 20-40 us each): out = [vals k | checks 2k + k^2 | scal 4 | ints 8 | mu n | vecs k n]
-__global__ void tica_solve_emit_kernel(const double* __restrict__ lam, const double* __restrict__ res, const double* __restrict__ scal,
-                                       const int* __restrict__ ints, const double* __restrict__ mu, const double* __restrict__ vecs,
-                                       int n, int k, double* __restrict__ out)
-{
-    const int nres = 2 * k + k * k;
-    const size_t o_res = k, o_scal = o_res + nres, o_ints = o_scal + 4, o_mu = o_ints + 8, o_vec = o_mu + n, total = o_vec + (size_t)k * n;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        double v;
-        if (e < o_res) v = lam[e];
-        else if (e < o_scal) v = res[e - o_res];
-        else if (e < o_ints) v = scal[e - o_scal];
-        else if (e < o_mu) v = (double)ints[e - o_ints];
-        else if (e < o_vec) v = mu[e - o_mu];
-        else v = vecs[e - o_vec];
-        out[e] = v;
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_tica_reduce(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, const double* scale, double* Cs, double* mu, double* info)
-{
-    if (!h || !Cs || !mu) return fail(MSM_ERR_STATE, "msm_tica_reduce: null argument");
-    SolveBufs b;
-    int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
-    if (rc) return rc;
-    const size_t FF = (size_t)h->g.F * h->g.F;
-    double scal[4];
-    int ints[8];
-    MSM_HIP_CHECK(hipMemcpyAsync(Cs, b.A, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(mu, b.mu, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(scal, b.scal, sizeof(scal), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(ints, b.ints, sizeof(ints), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    return tica_reduce_status(scal, ints, info);
-}
-
-int msm_tica_solve_topk(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, const double* scale, msm_idx_t k, double* vals,
-                        double* vecs, double* Cs, double* mu, double* info, int* status)
-{
-    if (!h || !vals || !vecs || !Cs || !mu || !status) return fail(MSM_ERR_STATE, "msm_tica_solve_topk: null argument");
-    if (h->g.F > 1024 || h->g.F < 128) return fail(MSM_ERR_INVALID, "msm_tica_solve_topk: need 128 <= n_features <= 1024");
-    if (k < 1 || k > 16) return fail(MSM_ERR_INVALID, "msm_tica_solve_topk: need 1 <= k <= 16");
-    SolveBufs b;
-    int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
-    if (rc) return rc;
-    const int n = h->g.F;
-    const size_t FF = (size_t)n * n;
-    // Chebyshev-filtered subspace iteration (subspace.hip): a few short launch chains when the spectrum has the gap tICA is
-    // run for; the reduced tICA matrix has its spectrum in [-1, 1].  When it does not converge (flat spectra: white-noise
-    // features) the reduced matrix goes back to the caller, whose verified fallback is LAPACK's dsyevr on it (round 3 had a
-    // second device route in between -- cooperative tridiagonalisation + multisection + inverse iteration; removed in round
-    // 4: two routes, one fallback).
-    int conv = 0, outer = 0;
-    // pinned host memory of the handle: [results of the solve | staging of the iteration's Rayleigh-Ritz steps]
-    const size_t pin_res = 17 + 320 + 12 + 17 * (size_t)n, pin_total = pin_res + subspace_pin_doubles();
-    if (h->solve_pin_n < pin_total) {
-        if (h->solve_pin) (void)hipHostFree(h->solve_pin);
-        h->solve_pin = nullptr;
-        h->solve_pin_n = 0;
-        MSM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h->solve_pin), pin_total * sizeof(double), hipHostMallocDefault));
-        h->solve_pin_n = pin_total;
-    }
-    // (Round 5 built the iteration QUEUED -- the 32 x 32 Rayleigh-Ritz problems by one-sided Jacobi in one workgroup, every decision
-    //  on the device, one synchronisation per solve -- and removed it again: a Jacobi round is a chain of shuffles, square roots
-    //  and divisions, ~0.5 us of latency, 31 rounds a sweep, and the kernel took 0.2 ms per Rayleigh-Ritz round against ~0.13 ms
-    //  for the two copies, two synchronisations and 25 us of host arithmetic it replaced: solve 1.26 ms against 1.08 ms.  DESIGN 3.9.)
-    if ((rc = subspace_topk_device(b.A, n, (int)k, -1.02, 5e-12, 10, 6, b.lam, b.Yk, b.sswork, h->solve_pin + pin_res, &conv, &outer,
-                                   0.0, 1.0)))   // prior: the reduced tICA matrix has its spectrum in [-1, 1], the noise bulk near 0
-        return rc;
-    if (!conv) {
-        double scal[4];
-        int ints[8];
-        MSM_HIP_CHECK(hipMemcpyAsync(Cs, b.A, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        MSM_HIP_CHECK(hipMemcpyAsync(mu, b.mu, n * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        MSM_HIP_CHECK(hipMemcpyAsync(scal, b.scal, sizeof(scal), hipMemcpyDeviceToHost, stream()));
-        MSM_HIP_CHECK(hipMemcpyAsync(ints, b.ints, sizeof(ints), hipMemcpyDeviceToHost, stream()));
-        MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-        rc = tica_reduce_status(scal, ints, info);
-        if (rc) return rc;
-        if (info) {
-            info[8] = 0.0;
-            info[9] = (double)outer;
-        }
-        *status = 1;
-        return MSM_OK;
-    }
-    if ((rc = pair_residual_device(b.A, n, b.Yk, b.lam, (int)k, b.res))) return rc;
-    // the vectors of the original problem: S = U^-1 Yk = W^T Yk (n <= 1024 here: W = U^-T was formed with the factor)
-    if ((rc = winv_back_device(b.Winv, n, b.Yk, (int)k, b.S))) return rc;
-    // one packed copy of everything the caller gets (b.Y, n^2 doubles, is free at this point)
-    const int nres = 2 * (int)k + (int)k * (int)k;
-    const size_t o_res = (size_t)k, o_scal = o_res + nres, o_ints = o_scal + 4, o_mu = o_ints + 8, o_vec = o_mu + n, total = o_vec + (size_t)k * n;
-    if (total > pin_res) return fail(MSM_ERR_STATE, "msm_tica_solve_topk: result staging too small");
-    hipLaunchKernelGGL(tica_solve_emit_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream(), b.lam, b.res, b.scal, b.ints, b.mu,
-                       b.S, n, (int)k, b.Y);
-    MSM_HIP_CHECK(hipGetLastError());
-    MSM_HIP_CHECK(hipMemcpyAsync(h->solve_pin, b.Y, total * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    const double* hp = h->solve_pin;
-    const double* res = hp + o_res;
-    double scal[4];
-    int ints[8];
-    for (int i = 0; i < 4; ++i) scal[i] = hp[o_scal + i];
-    for (int i = 0; i < 8; ++i) ints[i] = (int)hp[o_ints + i];
-    memcpy(vals, hp, (size_t)k * sizeof(double));
-    memcpy(mu, hp + o_mu, (size_t)n * sizeof(double));
-    memcpy(vecs, hp + o_vec, (size_t)k * n * sizeof(double));
-    rc = tica_reduce_status(scal, ints, info);
-    if (rc) return rc;
-    if (info) {
-        info[8] = 1.0;                // the pairs came from the subspace iteration
-        info[9] = (double)outer;      // filtered iterations spent (also when they did not converge)
-    }
-    // self-check on the reduced matrix: every returned pair must satisfy C y = lambda y to rounding, be normalised, and the
-    // k vectors must be mutually orthogonal (a rank-deficient block would pass the per-pair checks; the Gram
-    // matrix of the vectors comes from the residual kernel).  A failure hands the reduced matrix to the caller's LAPACK
-    // route instead of returning a wrong pair.
-    double lmax = 1.0, rmax = 0.0, nmax = 0.0, omax = 0.0;
-    for (int j = 0; j < (int)k; ++j) {
-        lmax = std::max(lmax, std::fabs(vals[j]));
-        rmax = std::max(rmax, res[j]);
-        nmax = std::max(nmax, res[k + j]);
-        for (int i = 0; i < j; ++i) {
-            const double dot = res[2 * k + (size_t)j * k + i];
-            omax = std::max(omax, (dot == dot) ? std::fabs(dot) : INFINITY);
-        }
-    }
-    if (info) {
-        info[6] = rmax;
-        info[7] = std::max(nmax, omax);
-    }
-    *status = (!(rmax <= 1e-11 * lmax) || !(nmax <= 1e-10) || !(omax <= 1e-8)) ? 2 : 0;
-    if (*status) {
-        MSM_HIP_CHECK(hipMemcpyAsync(Cs, b.A, FF * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    }
-    return MSM_OK;
-}
-
-int msm_tica_backsolve(msm_tica_t* h, const double* Y, msm_idx_t k, double* V)
-{
-    if (!h || !Y || !V) return fail(MSM_ERR_STATE, "msm_tica_backsolve: null argument");
-    if (!h->reduced) return fail(MSM_ERR_STATE, "msm_tica_backsolve: no reduced problem (call msm_tica_reduce first)");
-    if (k < 1 || k > h->g.F) return fail(MSM_ERR_INVALID, "msm_tica_backsolve: need 1 <= k <= n_features");
-    SolveBufs b;
-    int rc = solve_bufs(h, &b);
-    if (rc) return rc;
-    const size_t bytes = (size_t)k * h->g.F * sizeof(double);
-    MSM_HIP_CHECK(hipMemcpyAsync(b.Y, Y, bytes, hipMemcpyHostToDevice, stream()));
-    if (h->g.F <= 1024 && k <= 64) {
-        if ((rc = winv_back_device(b.Winv, h->g.F, b.Y, (int)k, b.S))) return rc;
-        MSM_HIP_CHECK(hipMemcpyAsync(V, b.S, bytes, hipMemcpyDeviceToHost, stream()));
-    } else {
-        if ((rc = sygv_back_device(b.B, b.Y, h->g.F, (int)k))) return rc;
-        MSM_HIP_CHECK(hipMemcpyAsync(V, b.Y, bytes, hipMemcpyDeviceToHost, stream()));
-    }
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    return MSM_OK;
-}
-
-int msm_tica_solve_device(msm_tica_t* h, double shrinkage, msm_idx_t n_rblw, const double* scale, msm_idx_t k,
-                          double* vals, double* vecs, double* mu, double* info)
-{
-    if (!h || !vals || !vecs || !mu) return fail(MSM_ERR_STATE, "msm_tica_solve_device: null argument");
-    if (k < 1 || k > h->g.F) return fail(MSM_ERR_INVALID, "msm_tica_solve_device: need 1 <= k <= n_features");
-    SolveBufs b;
-    int rc = tica_reduce_device(h, shrinkage, n_rblw, scale, &b);
-    if (rc) return rc;
-    const int n = h->g.F;
-    if ((rc = syevd_device(b.A, n, b.D, b.E, b.ints + 3))) return rc;
-    if ((rc = sygv_back_device(b.B, b.A + (size_t)(n - k) * n, n, (int)k))) return rc;
-    hipLaunchKernelGGL(tica_top_pairs_kernel, dim3((unsigned)ceil_div(n, 256), (unsigned)k), dim3(256), 0, stream(), b.A, b.D, n,
-                       (int)k, b.Y, b.vals);
-    MSM_HIP_CHECK(hipGetLastError());
-    double scal[4];
-    int ints[8];
-    MSM_HIP_CHECK(hipMemcpyAsync(vecs, b.Y, (size_t)k * n * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(vals, b.vals, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(mu, b.mu, n * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(scal, b.scal, sizeof(scal), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(ints, b.ints, sizeof(ints), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    h->reduced = false;  // A was overwritten by the eigenvectors
-    rc = tica_reduce_status(scal, ints, info);
-    if (rc) return rc;
-    if (ints[3] != 0) return fail(MSM_ERR_INVALID, "eigenvalue iteration did not converge (info = %d)", ints[3]);
-    return MSM_OK;
-}
-
 int msm_tica_counts(msm_tica_t* h, msm_idx_t* n_observations, msm_idx_t* n_sequences)
 {
     if (!h) return fail(MSM_ERR_STATE, "null tica handle");
@@ -1806,355 +1442,7 @@ int msm_tica_allreduce(msm_tica_t* h)
 int msm_tica_export_sums(msm_tica_t* h, double* s0, double* stau)
 {
     if (!h || !s0 || !stau) return fail(MSM_ERR_STATE, "null argument");
-    int rc = tica_export_device(h);
-    if (rc) return rc;
-    const size_t FF = (size_t)h->g.F * h->g.F;
-    MSM_HIP_CHECK(hipMemcpyAsync(s0, h->packed + 2 * FF, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(stau, h->packed + 2 * FF + h->g.F, h->g.F * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));
-    return MSM_OK;
-}
-
-}  // extern "C"
-
-// ---- projection: parameters on the device (once per call) and the launches for one device-resident matrix
-struct ProjParams {
-    double* dmean = nullptr;    // mean @ comps^T (k values)
-    double* dcomps = nullptr;   // [k][F]
-    double* dVp = nullptr;      // [ceil(k / 16)][F][16] panels of the fp64-MFMA path
-    int* dflag = nullptr;       // non-finite input seen
-    std::vector<double> muV, vp;   // host sources of the uploads: alive until the caller has synchronised
-};
-
-// host sources of the projection's uploads: muV = mean @ comps^T, and the components in blocks of 16 as panels Vp[F][16]
-// (feature-major, zero padded) for the fp64-MFMA path
-static void proj_host_params(const double* mean, const double* comps, msm_idx_t k, msm_idx_t n_features, std::vector<double>& muV,
-                             std::vector<double>& vp)
-{
-    muV.assign((size_t)k, 0.0);
-    vp.assign((size_t)ceil_div(k, 16) * n_features * 16, 0.0);
-    for (msm_idx_t c = 0; c < k; ++c) {
-        double sacc = 0.0;
-        for (msm_idx_t f = 0; f < n_features; ++f) {
-            sacc += mean[f] * comps[c * n_features + f];
-            vp[((size_t)(c / 16) * n_features + f) * 16 + (c % 16)] = comps[c * n_features + f];
-        }
-        muV[(size_t)c] = sacc;
-    }
-}
-
-// the fp64-MFMA projection, one launch of `grid` workgroups per block of 16 components: rows of X[n_rows][ldd] into outd, or
-// -- `tiles` -- one tile of up to 256 rows per workgroup
-template <typename T>
-static void proj_mfma_blocks(unsigned grid, const void* Xd, long long n_rows, msm_idx_t n_features, long long ldd, const double* dmean,
-                             const double* dVp, msm_idx_t k, double* outd, int* dflag, const ProjTile* tiles)
-{
-    for (msm_idx_t kb = 0; kb < ceil_div(k, 16); ++kb)
-        hipLaunchKernelGGL((tica_project_mfma_kernel<T>), dim3(grid), dim3(NT), 0, stream(), (const T*)Xd, n_rows, (int)n_features, ldd,
-                           dmean, dVp + (size_t)kb * n_features * 16, (int)std::min<msm_idx_t>(16, k - kb * 16), (int)(kb * 16), (int)k,
-                           outd, dflag, tiles);
-}
-static int proj_launch_mfma(int dtype_bytes, unsigned grid, const void* Xd, long long n_rows, msm_idx_t n_features, long long ldd,
-                            const double* dmean, const double* dVp, msm_idx_t k, double* outd, int* dflag, const ProjTile* tiles)
-{
-    if (dtype_bytes == 2) proj_mfma_blocks<Bf16Raw>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
-    else if (dtype_bytes == 4) proj_mfma_blocks<float>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
-    else proj_mfma_blocks<double>(grid, Xd, n_rows, n_features, ldd, dmean, dVp, k, outd, dflag, tiles);
-    MSM_HIP_CHECK(hipGetLastError());
-    return MSM_OK;
-}
-
-static int proj_upload(ProjParams& Q, const double* mean, const double* comps, msm_idx_t k, msm_idx_t n_features)
-{
-    DevBuf &dPar = pool(PS_PAR), &dVp = pool(PS_W);
-    int rc;
-    const size_t par_n = (size_t)k + (size_t)k * n_features;
-    const msm_idx_t nkb = ceil_div(k, 16);
-    if ((rc = dPar.reserve(par_n * sizeof(double) + 16))) return rc;
-    if ((rc = dVp.reserve((size_t)nkb * n_features * 16 * sizeof(double)))) return rc;
-    proj_host_params(mean, comps, k, n_features, Q.muV, Q.vp);
-    Q.dmean = dPar.as<double>();
-    Q.dcomps = Q.dmean + k;
-    Q.dflag = reinterpret_cast<int*>(Q.dcomps + (size_t)k * n_features);
-    Q.dVp = dVp.as<double>();
-    MSM_HIP_CHECK(hipMemcpyAsync(Q.dmean, Q.muV.data(), k * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(Q.dcomps, comps, (size_t)k * n_features * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(Q.dVp, Q.vp.data(), Q.vp.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemsetAsync(Q.dflag, 0, sizeof(int), stream()));
-    return MSM_OK;
-}
-
-// Which projection kernel rows of n_features elements at row stride ld take, decided in ONE place (exported to the tests as
-// msm_tica_project_plan; pure).  Rows that are whole 16-byte vectors at 16-byte aligned addresses are read with vector
-// loads; they go to the fp64-MFMA kernel while a 256-row tile spans less than 2^32 bytes (its row offsets are 32-bit), to the
-// lane-per-row kernel with vector loads beyond, and every other row to the lane-per-row kernel element by element.
-struct ProjPlan {
-    int kernel, vec;
-};
-static ProjPlan proj_plan(int dtype_bytes, msm_idx_t n_features, msm_idx_t ld, bool aligned16)
-{
-    const int cw = 16 / dtype_bytes;
-    const int vec = aligned16 && (ld % cw == 0) && (n_features % cw == 0);
-    const bool mfma = vec && (size_t)256 * ld * dtype_bytes < ((size_t)1 << 32);
-    return ProjPlan{mfma ? MSM_PJ_MFMA : MSM_PJ_ROWS, vec};
-}
-
-static long long g_pj_stats[2] = {0, 0};   // groups of the last host-list call, tiles of the last batch call
-
-// out[n_rows][k] (device) = (X - mean) comps^T for the device-resident X[n_rows][ldd]; queued on stream(), nothing synchronised
-static int proj_launch(const ProjParams& Q, const void* Xd, int dtype_bytes, msm_idx_t n_rows, msm_idx_t n_features, msm_idx_t ldd,
-                       msm_idx_t k, double* outd)
-{
-    const unsigned grid = (unsigned)ceil_div(n_rows, 128);
-    const ProjPlan pl = proj_plan(dtype_bytes, n_features, ldd, ((uintptr_t)Xd) % 16 == 0);
-    const int vec = pl.vec;
-    if (pl.kernel == MSM_PJ_MFMA) {
-        return proj_launch_mfma(dtype_bytes, (unsigned)ceil_div(n_rows, 256), Xd, n_rows, n_features, ldd, Q.dmean, Q.dVp, k, outd, Q.dflag, nullptr);
-    }
-    const int npw = (int)std::min<msm_idx_t>(8, ceil_div(k, 4));  // components per wave
-    double* dmean = Q.dmean;
-    double* dcomps = Q.dcomps;
-    int* dflag = Q.dflag;
-#define MSM_PROJ(TT, NN)                                                                              \
-    hipLaunchKernelGGL((tica_project_kernel<TT, NN>), dim3(grid), dim3(NT), 0, stream(), (const TT*)Xd, \
-                       (long long)n_rows, (int)n_features, (long long)ldd, dmean, dcomps, (int)k, outd, dflag, vec)
-#define MSM_PROJ_T(TT)                                                                                \
-    switch (npw) {                                                                                    \
-    case 1: MSM_PROJ(TT, 1); break;                                                                   \
-    case 2: MSM_PROJ(TT, 2); break;                                                                   \
-    case 3: MSM_PROJ(TT, 3); break;                                                                   \
-    case 4: MSM_PROJ(TT, 4); break;                                                                   \
-    case 5: MSM_PROJ(TT, 5); break;                                                                   \
-    case 6: MSM_PROJ(TT, 6); break;                                                                   \
-    case 7: MSM_PROJ(TT, 7); break;                                                                   \
-    default: MSM_PROJ(TT, 8); break;                                                                  \
-    }
-    if (dtype_bytes == 2) {
-        MSM_PROJ_T(Bf16Raw)
-    } else if (dtype_bytes == 4) {
-        MSM_PROJ_T(float)
-    } else {
-        MSM_PROJ_T(double)
-    }
-#undef MSM_PROJ_T
-#undef MSM_PROJ
-    MSM_HIP_CHECK(hipGetLastError());
-    return MSM_OK;
-}
-
-extern "C" {
-
-int msm_tica_project(const void* X, int dtype_bytes, msm_idx_t n_rows, msm_idx_t n_features,
-                     msm_idx_t ld, const double* mean, const double* comps, msm_idx_t k,
-                     double* out, int on_device, int check_finite)
-{
-    if (!X || !mean || !comps || !out) return fail(MSM_ERR_INVALID, "msm_tica_project: null pointer");
-    if (dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8)
-        return fail(MSM_ERR_INVALID, "dtype_bytes must be 2 (bfloat16), 4 or 8");
-    if (n_rows < 0 || n_features < 1 || k < 1 || ld < n_features) return fail(MSM_ERR_INVALID, "bad shape");
-    if (n_rows == 0) return MSM_OK;
-    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
-    DevBuf &dX = pool(PS_X), &dOut = pool(PS_OUT);
-    int rc;
-    ProjParams Q;
-    if ((rc = proj_upload(Q, mean, comps, k, n_features))) return rc;
-    const void* Xd = X;
-    double* outd = out;
-    msm_idx_t ldd = ld;
-    if (!on_device) {
-        if ((rc = dX.reserve((size_t)n_rows * n_features * dtype_bytes))) return rc;
-        if ((rc = dOut.reserve((size_t)n_rows * k * sizeof(double)))) return rc;
-        if (ld == n_features) {
-            if ((rc = h2d_bulk(dX.p, X, (size_t)n_rows * n_features * dtype_bytes))) return rc;
-        } else {
-            MSM_HIP_CHECK(hipMemcpy2DAsync(dX.p, (size_t)n_features * dtype_bytes, X, (size_t)ld * dtype_bytes,
-                                           (size_t)n_features * dtype_bytes, (size_t)n_rows, hipMemcpyHostToDevice, stream()));
-        }
-        Xd = dX.p;
-        outd = dOut.as<double>();
-        ldd = n_features;
-    }
-    if ((rc = proj_launch(Q, Xd, dtype_bytes, n_rows, n_features, ldd, k, outd))) return rc;
-    if (!on_device) {
-        int rcd = d2h_bulk(out, outd, (size_t)n_rows * k * sizeof(double));
-        if (rcd) return rcd;
-    }
-    int f = 0;
-    if (check_finite) MSM_HIP_CHECK(hipMemcpyAsync(&f, Q.dflag, sizeof(int), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));  // the uploads' host sources and the scratch buffers die with this frame
-    if (check_finite && f) return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
-    return MSM_OK;
-}
-
-/* msm_tica_project for a LIST of HOST trajectories (contiguous rows of n_features values): out (host) is ONE
- * [sum of n_rows][k] float64 array, trajectory after trajectory.  The rows are staged in groups of 512 MiB through the two
- * halves of a device buffer -- group g + 1 is copied while group g is projected (one launch per group: the projection is
- * row by row) --, the result stays on the device until ONE copy at the end.  A call per trajectory (msm_tica_project) is
- * copy, kernel, copy back, synchronise: 27 GB/s on 100 x (10,000 x 512 f32) against the link's 56 (scripts/apiprobe.py). */
-int msm_tica_project_host_list(const void* const* X_ptrs, const msm_idx_t* n_rows, msm_idx_t n_seq, int dtype_bytes,
-                               msm_idx_t n_features, const double* mean, const double* comps, msm_idx_t k, double* out,
-                               int check_finite)
-{
-    if (!X_ptrs || !n_rows || !mean || !comps || !out) return fail(MSM_ERR_INVALID, "msm_tica_project_host_list: null pointer");
-    if (dtype_bytes != 4 && dtype_bytes != 8) return fail(MSM_ERR_INVALID, "dtype_bytes must be 4 or 8");
-    if (n_seq < 0 || n_features < 1 || k < 1) return fail(MSM_ERR_INVALID, "bad shape");
-    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
-    size_t total = 0;
-    for (msm_idx_t s = 0; s < n_seq; ++s) {
-        if (n_rows[s] < 0 || (n_rows[s] > 0 && !X_ptrs[s])) return fail(MSM_ERR_INVALID, "bad sequence %lld", (long long)s);
-        total += (size_t)n_rows[s];
-    }
-    g_pj_stats[0] = 0;
-    if (total == 0) return MSM_OK;
-    const size_t row_bytes = (size_t)n_features * dtype_bytes;
-    size_t budget = (size_t)512 << 20;
-    if (const char* be = getenv("MSM_TICA_PROJ_GROUP_BYTES")) {   // bytes per group (the tests' group seams at small sizes); read per call
-        const long long b = atoll(be);
-        if (b > 0) budget = (size_t)b;
-    }
-    // groups of whole trajectories, rows packed back to back (a trajectory larger than the budget is a group of its own)
-    std::vector<msm_idx_t> gend;
-    size_t half = 0;
-    {
-        size_t bytes = 0;
-        for (msm_idx_t s = 0; s < n_seq; ++s) {
-            const size_t b = (size_t)n_rows[s] * row_bytes;
-            if (bytes > 0 && bytes + b > budget) {
-                gend.push_back(s);
-                half = std::max(half, bytes);
-                bytes = 0;
-            }
-            bytes += b;
-        }
-        gend.push_back(n_seq);
-        half = std::max(half, bytes);
-    }
-    half = (half + 255) & ~(size_t)255;
-    g_pj_stats[0] = (long long)gend.size();
-    DevBuf &dX = pool(PS_X), &dOut = pool(PS_OUT);
-    int rc;
-    if ((rc = dX.reserve(2 * half))) return rc;
-    if ((rc = dOut.reserve(total * k * sizeof(double)))) return rc;
-    ProjParams Q;
-    if ((rc = proj_upload(Q, mean, comps, k, n_features))) return rc;
-    hipEvent_t evk[2] = {nullptr, nullptr};   // the projection of the group that last used a half has finished
-    for (auto& e : evk) MSM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    auto cleanup = [&](int code) {
-        (void)hipStreamSynchronize(stream());
-        for (auto& e : evk)
-            if (e) (void)hipEventDestroy(e);
-        return code;
-    };
-    auto copy_group = [&](size_t g, bool first) -> int {
-        char* d = dX.as<char>() + (g & 1) * half;
-        for (msm_idx_t s = g ? gend[g - 1] : 0; s < gend[g]; ++s) {
-            const size_t b = (size_t)n_rows[s] * row_bytes;
-            if (b) {
-                const int rcb = h2d_bulk(d, X_ptrs[s], b, first);
-                if (rcb) return rcb;
-            }
-            d += b;
-        }
-        return MSM_OK;
-    };
-    if ((rc = copy_group(0, true))) return cleanup(rc);
-    size_t row0 = 0;
-    for (size_t g = 0; g < gend.size(); ++g) {
-        size_t rows = 0;
-        for (msm_idx_t s = g ? gend[g - 1] : 0; s < gend[g]; ++s) rows += (size_t)n_rows[s];
-        if (rows) {
-            rc = proj_launch(Q, dX.as<char>() + (g & 1) * half, dtype_bytes, (msm_idx_t)rows, n_features, n_features, k,
-                             dOut.as<double>() + row0 * k);
-            if (rc) return cleanup(rc);
-        }
-        if (hipEventRecord(evk[g & 1], stream()) != hipSuccess) return cleanup(fail(MSM_ERR_HIP, "hipEventRecord failed"));
-        row0 += rows;
-        if (g + 1 < gend.size()) {
-            // the other half was last read by the projection of group g - 1 (queued before this one)
-            if (g >= 1 && hipEventSynchronize(evk[(g + 1) & 1]) != hipSuccess) return cleanup(fail(MSM_ERR_HIP, "hipEventSynchronize failed"));
-            if ((rc = copy_group(g + 1, false))) return cleanup(rc);
-        }
-    }
-    if ((rc = d2h_bulk(out, dOut.p, total * k * sizeof(double)))) return cleanup(rc);
-    int f = 0;
-    if (check_finite && hipMemcpyAsync(&f, Q.dflag, sizeof(int), hipMemcpyDeviceToHost, stream()) != hipSuccess)
-        return cleanup(fail(MSM_ERR_HIP, "hipMemcpyAsync failed"));
-    rc = cleanup(MSM_OK);
-    if (check_finite && f) return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
-    return rc;
-}
-
-/* msm_tica_project for a LIST of device-resident trajectories in one launch per block of 16 components: X_ptrs[s] is
- * [n_rows[s], n_features] (row stride n_features), out_ptrs[s] its [n_rows[s], k] float64 output.  Needs 16-byte aligned
- * rows (n_features a multiple of 16 / dtype_bytes, aligned base pointers); returns MSM_ERR_INVALID otherwise and the
- * caller projects trajectory by trajectory.  (tica.py:329-352 walks the list; a launch per 10,000-frame trajectory keeps a
- * sixth of the GPU busy.) */
-int msm_tica_project_batch(const void* const* X_ptrs, double* const* out_ptrs, const msm_idx_t* n_rows, msm_idx_t n_seq, int dtype_bytes,
-                           msm_idx_t n_features, const double* mean, const double* comps, msm_idx_t k, int check_finite)
-{
-    if (!X_ptrs || !out_ptrs || !n_rows || !mean || !comps) return fail(MSM_ERR_INVALID, "msm_tica_project_batch: null pointer");
-    if (dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8)
-        return fail(MSM_ERR_INVALID, "dtype_bytes must be 2 (bfloat16), 4 or 8");
-    if (n_seq < 0 || n_features < 1 || k < 1) return fail(MSM_ERR_INVALID, "bad shape");
-    if (msm_device_count() == 0) return fail(MSM_ERR_NODEVICE, "no HIP device visible");
-    g_pj_stats[1] = 0;
-    if (proj_plan(dtype_bytes, n_features, n_features, true).kernel != MSM_PJ_MFMA)   // whole 16-byte vectors, 32-bit tile offsets
-        return fail(MSM_ERR_INVALID, "msm_tica_project_batch: rows must be whole 16-byte vectors");
-    std::vector<ProjTile> tiles;
-    for (msm_idx_t s = 0; s < n_seq; ++s) {
-        if (n_rows[s] < 0) return fail(MSM_ERR_INVALID, "bad shape");
-        if (n_rows[s] == 0) continue;
-        if (!X_ptrs[s] || !out_ptrs[s]) return fail(MSM_ERR_INVALID, "msm_tica_project_batch: null pointer");
-        if (((uintptr_t)X_ptrs[s]) % 16 != 0) return fail(MSM_ERR_INVALID, "msm_tica_project_batch: rows must be 16-byte aligned");
-        for (msm_idx_t r = 0; r < n_rows[s]; r += 256) {
-            ProjTile t;
-            t.x = static_cast<const char*>(X_ptrs[s]) + (size_t)r * n_features * dtype_bytes;
-            t.out = out_ptrs[s] + (size_t)r * k;
-            t.rows = n_rows[s] - r;
-            tiles.push_back(t);
-        }
-    }
-    g_pj_stats[1] = (long long)tiles.size();
-    if (tiles.empty()) return MSM_OK;
-    int rc;
-    DevBuf &dPar = pool(PS_PAR), &dVp = pool(PS_W), &dT = pool(PS_IDX);
-    const msm_idx_t nkb = ceil_div(k, 16);
-    if ((rc = dPar.reserve((size_t)k * sizeof(double) + 16))) return rc;
-    if ((rc = dVp.reserve((size_t)nkb * n_features * 16 * sizeof(double)))) return rc;
-    if ((rc = dT.reserve(tiles.size() * sizeof(ProjTile)))) return rc;
-    std::vector<double> muV, vp;
-    proj_host_params(mean, comps, k, n_features, muV, vp);
-    double* dmean = dPar.as<double>();
-    int* dflag = reinterpret_cast<int*>(dmean + k);
-    MSM_HIP_CHECK(hipMemcpyAsync(dmean, muV.data(), k * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemsetAsync(dflag, 0, sizeof(int), stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(dVp.p, vp.data(), vp.size() * sizeof(double), hipMemcpyHostToDevice, stream()));
-    MSM_HIP_CHECK(hipMemcpyAsync(dT.p, tiles.data(), tiles.size() * sizeof(ProjTile), hipMemcpyHostToDevice, stream()));
-    if ((rc = proj_launch_mfma(dtype_bytes, (unsigned)tiles.size(), nullptr, 0LL, n_features, (long long)n_features, dmean, dVp.as<double>(), k,
-                               nullptr, dflag, dT.as<ProjTile>())))
-        return rc;
-    int f2 = 0;
-    if (check_finite) MSM_HIP_CHECK(hipMemcpyAsync(&f2, dflag, sizeof(int), hipMemcpyDeviceToHost, stream()));
-    MSM_HIP_CHECK(hipStreamSynchronize(stream()));   // `tiles`, `vp` and `muV` die with this frame
-    if (check_finite && f2) return fail(MSM_ERR_NONFINITE, "Input contains NaN, infinity or a value too large");
-    return MSM_OK;
-}
-
-int msm_tica_project_plan(int dtype_bytes, msm_idx_t n_features, msm_idx_t ld, int aligned16, int* kernel, int* vec)
-{
-    if ((dtype_bytes != 2 && dtype_bytes != 4 && dtype_bytes != 8) || n_features < 1 || ld < n_features || !kernel || !vec)
-        return fail(MSM_ERR_INVALID, "msm_tica_project_plan: bad argument");
-    const ProjPlan pl = proj_plan(dtype_bytes, n_features, ld, aligned16 != 0);
-    *kernel = pl.kernel;
-    *vec = pl.vec;
-    return MSM_OK;
-}
-
-int msm_tica_project_last_stats(msm_idx_t* out2)
-{
-    if (!out2) return fail(MSM_ERR_INVALID, "msm_tica_project_last_stats: null pointer");
-    for (int i = 0; i < 2; ++i) out2[i] = g_pj_stats[i];
-    return MSM_OK;
+    return msm_tica_export(h, nullptr, nullptr, s0, stau, nullptr, nullptr);
 }
 
 }  // extern "C"

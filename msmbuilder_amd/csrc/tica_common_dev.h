@@ -1,5 +1,5 @@
 // tica_common_dev.h -- constants, chunk / argument structs and block-id helpers shared by the tICA kernels
-// (round 5: cut out of tica.hip by kernel family, unchanged; included by it in this order)
+// (round 5: cut out of tica.hip by kernel family, unchanged; shared by tica.hip, tica_solve.hip and tica_project.hip)
 #pragma once
 #include "common.h"
 

@@ -1,5 +1,5 @@
 // tica_project_dev.h -- tica_project_kernel / tica_project_mfma_kernel (transform)
-// (round 5: cut out of tica.hip by kernel family, unchanged; included by it in this order)
+// (round 5: cut out of tica.hip by kernel family, unchanged; included by tica_project.hip alone)
 #pragma once
 #include "tica_common_dev.h"
 

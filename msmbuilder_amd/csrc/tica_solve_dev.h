@@ -1,5 +1,5 @@
 // tica_solve_dev.h -- finalise / RBLW / shrink / top-pairs kernels of the device-resident solve
-// (round 5: cut out of tica.hip by kernel family, unchanged; included by it in this order)
+// (round 5: cut out of tica.hip by kernel family, unchanged; included by tica_solve.hip alone)
 #pragma once
 #include "tica_common_dev.h"
 

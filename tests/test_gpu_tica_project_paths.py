@@ -408,6 +408,68 @@ def test_offset_family_through_both_kernels_and_the_batch(L, dt):
             assert_within(g, p, mean, V, "offset rows through the batch")
 
 
+# ------------------------------------------------------------------ the narrowest rows through the tile table
+def test_batch_two_component_blocks_at_four_features(L):
+    """The batch entry at the smallest width that is whole 16-byte vectors (4 float32 features) with k = 17, two blocks of
+    components, on trajectories of 1, 255 and 257 rows: the tile table uploads no k x F components, and its flag sits right
+    behind the k means."""
+    nb, F, k, lens = 4, 4, 17, [1, 255, 257]
+    X, mean, V = R.make_case("plain", sum(lens), F, k, "f32")
+    parts = _cut(X, lens)
+    tensors = [to_dev(p) for p in parts]
+    rc, gots = _batch(L, tensors, lens, nb, F, mean, V)
+    assert rc == 0 and last_stats(L)[1] == len(R.tiles_ref(lens)) == 4
+    for s, (p, t, g) in enumerate(zip(parts, tensors, gots)):
+        assert_within(g, p, mean, V, "trajectory %d of %r rows, 4 features" % (s, lens))
+        rc1, one = project(L, t.data_ptr(), nb, len(p), F, F, mean, V)
+        assert rc1 == 0 and np.array_equal(bits(one), bits(g))
+    bad = parts[2].copy()
+    bad[256, 3] = np.inf
+    rc, _ = _batch(L, tensors[:2] + [to_dev(bad)], lens, nb, F, mean, V)
+    from msmbuilder_amd import _lib
+    assert rc == _lib.MSM_ERR_NONFINITE
+    rc, again = _batch(L, tensors, lens, nb, F, mean, V)
+    assert rc == 0 and all(np.array_equal(bits(a), bits(g)) for a, g in zip(again, gots))
+
+
+# ------------------------------------------------------------------ argument checks
+def test_entries_refuse_bad_arguments_with_their_own_messages(L):
+    """The argument checks of the three entries: MSM_ERR_INVALID before any device work, each entry named in its null-pointer
+    message, bfloat16 rows (dtype_bytes 2) refused by the host list alone, and no rows at all is not an error."""
+    from msmbuilder_amd import _lib
+    F, k, n = 4, 2, 3
+    X = np.zeros((n, F), np.float32)
+    mean, V, out = np.zeros(F), np.zeros((k, F)), np.full((n, k), SENT)
+    xp, op, rows = (C.c_void_p * 1)(X.ctypes.data), (C.c_void_p * 1)(out.ctypes.data), (C.c_int64 * 1)(n)
+    m, v, o = mean.ctypes.data, V.ctypes.data, C.c_void_p(out.ctypes.data)
+    x = C.c_void_p(X.ctypes.data)
+
+    def refused(rc, message):
+        assert rc == _lib.MSM_ERR_INVALID and _lib.last_error() == message, (rc, _lib.last_error())
+
+    refused(L.msm_tica_project(None, 4, n, F, F, m, v, k, o, 0, 1), "msm_tica_project: null pointer")
+    refused(L.msm_tica_project(x, 4, n, F, F, m, None, k, o, 0, 1), "msm_tica_project: null pointer")
+    refused(L.msm_tica_project(x, 3, n, F, F, m, v, k, o, 0, 1), "dtype_bytes must be 2 (bfloat16), 4 or 8")
+    for shape in ((-1, F, F, k), (n, 0, F, k), (n, F, F - 1, k), (n, F, F, 0)):
+        refused(L.msm_tica_project(x, 4, shape[0], shape[1], shape[2], m, v, shape[3], o, 0, 1), "bad shape")
+    assert L.msm_tica_project(x, 4, 0, F, F, m, v, k, o, 0, 1) == 0
+
+    refused(L.msm_tica_project_host_list(None, rows, 1, 4, F, m, v, k, o, 1), "msm_tica_project_host_list: null pointer")
+    refused(L.msm_tica_project_host_list(xp, rows, 1, 4, F, m, v, k, None, 1), "msm_tica_project_host_list: null pointer")
+    refused(L.msm_tica_project_host_list(xp, rows, 1, 2, F, m, v, k, o, 1), "dtype_bytes must be 4 or 8")
+    for shape in ((-1, F, k), (1, 0, k), (1, F, 0)):
+        refused(L.msm_tica_project_host_list(xp, rows, shape[0], 4, shape[1], m, v, shape[2], o, 1), "bad shape")
+    assert L.msm_tica_project_host_list(xp, rows, 0, 4, F, m, v, k, o, 1) == 0
+
+    refused(L.msm_tica_project_batch(xp, None, rows, 1, 4, F, m, v, k, 1), "msm_tica_project_batch: null pointer")
+    refused(L.msm_tica_project_batch(xp, op, rows, 1, 4, F, None, v, k, 1), "msm_tica_project_batch: null pointer")
+    refused(L.msm_tica_project_batch(xp, op, rows, 1, 16, F, m, v, k, 1), "dtype_bytes must be 2 (bfloat16), 4 or 8")
+    for shape in ((-1, F, k), (1, 0, k), (1, F, 0)):
+        refused(L.msm_tica_project_batch(xp, op, rows, shape[0], 4, shape[1], m, v, shape[2], 1), "bad shape")
+    assert L.msm_tica_project_batch(xp, op, rows, 0, 4, F, m, v, k, 1) == 0
+    assert np.all(bits(out) == SENT_BITS)
+
+
 # ------------------------------------------------------------------ tICA.transform
 def test_transform_routes(L):
     """The dispatch of tICA.transform: lists that must fall back to a call per trajectory (mixed dtypes, a misaligned device
