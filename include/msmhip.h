@@ -673,6 +673,44 @@ int msm_bace_fit(const double* counts, const double* w, const int32_t* keep, msm
                  float* values, msm_idx_t capacity, msm_idx_t* n_records, float* ms3, int on_device);
 int msm_bace_plan(msm_idx_t* out6);
 
+/* ---- PCCA+ objectives (lumping/pcca_plus.py) on a transition matrix that stays on the device ------------------------------
+ * A handle keeps T (n x n, row-major), pi (n) and V (n x m, row-major: the first m right eigenvectors, column 0 used as
+ * given) on the device; everything is float64.  2 <= m <= 64, m <= n <= 16384.
+ *   msm_pcca_create: T, pi and V follow on_device.  Also computes G = V^T diag(pi) T V (m x m) and w = V^T pi with one read
+ *     of T from memory: for chi = V A, chi_i^T diag(pi) T chi_i = (A^T G A)_ii and chi_i^T pi = (A^T w)_i.
+ *   msm_pcca_moments: G and w to host arrays.
+ *   msm_pcca_chi: fill_A of the reference applied to A_in (host, m x m; only A_in[1:, 1:] is read), on the device:
+ *       A[k, 0] = -sum_c A[k, c] (c >= 1);  A[0, c] = -min over the states of (V[:, 1:] A[1:])[., c];  A /= sum_c A[0, c];
+ *     then chi = V A (n x m) and mapping = the first maximum of each row of chi, a row with a NaN mapping to its first NaN
+ *     (numpy.argmax).  A_out, chi_out (nullable) and mapping_out (int32) are host arrays.
+ *   msm_pcca_objective: alpha (host) = the (m-1)^2 entries of A[1:, 1:], row-major; kind 0 crispness, 1 metastability,
+ *     2 crisp_metastability.  A, chi and the mapping as above.  *value = -inf where some macrostate receives no state or where
+ *     |(1 - sum A[0, 1:]) - (-min_s V[s, 1:] . A[1:, 0])| > 1e-8 (a NaN there fails); otherwise
+ *       crispness = sum_i (A^T A)_ii / A[0, i];   metastability = sum_i (A^T G A)_ii / (A^T w)_i;
+ *       crisp_metastability = sum_i num_i / den_i,  num_i = sum_{a in i} pi_a sum_{b in i} T[a, b],  den_i = sum_{a in i} pi_a.
+ *     The value is the objective itself (a minimiser negates it).  info (int32 x 4) = {feasible, macrostates used, mapping
+ *     equal to the previous evaluation's, passes over T made by this call}.  One upload, a queue of kernels with no host
+ *     synchronisation in between, one read-back.  The handle remembers the last mapping and its block sums: an equal mapping
+ *     gets its kind-2 value from them without a pass over T.  MSM_PCCA_REUSE=0 (read at every call) forces the pass; the bits
+ *     are the same.
+ *   msm_pcca_crisp: num and den (host, m each) of any mapping (host int32, values in [0, m)): the row kernel alone.
+ *   msm_pcca_plan: out5 = {rows of T per workgroup, columns per pass of a wave, threads per workgroup, largest n, largest m}.
+ * Orders of the m-term formulas, every product and sum rounded on its own: (A^T A)_ii adds A[k, i]^2 in ascending k;
+ * (A^T G A)_ii adds A[j, i] * (sum_k G[j, k] A[k, i], ascending k) in ascending j, (A^T w)_i adds A[j, i] w[j] in ascending j;
+ * the quotients are added in ascending i.
+ * No floating-point atomics: every sum is taken in an order fixed by n and m (pcca_dev.h), so results are the same bits from
+ * run to run, for host and device inputs, and under MSM_PCCA_MAX_GRID (read at every call), which caps the workgroups of the
+ * grid-stride kernels for the tests.
+ * MSM_ERR_INVALID: null pointers, m or n out of range (before any device work), a mapping value out of range, a bad kind. */
+typedef struct msm_pcca msm_pcca_t;
+int msm_pcca_create(const double* T, const double* pi, const double* V, msm_idx_t n, msm_idx_t m, int on_device, msm_pcca_t** handle);
+int msm_pcca_destroy(msm_pcca_t* handle);
+int msm_pcca_moments(msm_pcca_t* handle, double* G, double* w);
+int msm_pcca_chi(msm_pcca_t* handle, const double* A_in, double* A_out, double* chi_out, int32_t* mapping_out);
+int msm_pcca_objective(msm_pcca_t* handle, int kind, const double* alpha, double* value, int32_t* info);
+int msm_pcca_crisp(msm_pcca_t* handle, const int32_t* mapping, double* num, double* den);
+int msm_pcca_plan(msm_idx_t* out5);
+
 /* ---- Nystroem kernel feature map (decomposition/kernel_approximation.py, ktica.py) ------------------------------------
  * out[i, :] = k(rows[i], landmarks) . B - c     (rows: n x n_features at row stride ld elements; landmarks: L x
  * n_features of the rows' dtype; B: L x P float64; c: P float64 or NULL; landmarks, B and c are HOST arrays).

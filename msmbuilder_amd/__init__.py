@@ -12,5 +12,5 @@ from .cluster import (KCenters, KMeans, KMedoids, LandmarkAgglomerative, MiniBat
                       RegularSpatial)
 from .decomposition import KernelTICA, LandmarkNystroem, Nystroem, SparseTICA, tICA  # noqa: F401
 from .hmm import GaussianHMM, VonMisesHMM  # noqa: F401
-from .lumping import MVCA, BACE  # noqa: F401
+from .lumping import MVCA, BACE, PCCA, PCCAPlus  # noqa: F401
 from .msm import MarkovStateModel  # noqa: F401

@@ -159,6 +159,13 @@ def _declare(lib):
     f("msm_bace_pairs", C.c_int, _p, _p, _p, _p, _i64, _i64, _p, _p, C.c_int)
     f("msm_bace_fit", C.c_int, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64p, _p, C.c_int)
     f("msm_bace_plan", C.c_int, _i64p)
+    f("msm_pcca_create", C.c_int, _p, _p, _p, _i64, _i64, C.c_int, C.POINTER(_p))
+    f("msm_pcca_destroy", C.c_int, _p)
+    f("msm_pcca_moments", C.c_int, _p, _p, _p)
+    f("msm_pcca_chi", C.c_int, _p, _p, _p, _p, _p)
+    f("msm_pcca_objective", C.c_int, _p, C.c_int, _p, _f64p, _p)
+    f("msm_pcca_crisp", C.c_int, _p, _p, _p, _p)
+    f("msm_pcca_plan", C.c_int, _i64p)
     f("msm_kernel_map_plan", C.c_int, _i64, _i64, _i64, C.c_int, _i64p)
     for sfx in ("f32", "f64"):
         f("msm_kernel_map_" + sfx, C.c_int, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, C.c_int, C.c_double, C.c_double,
